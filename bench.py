@@ -12,10 +12,15 @@ combines the bands (the multi-GPU split lives behind the drop-in boundary):
     unmodified client gets from the "gpus" render parameter), one host thread + stream per GPU,
     member 0 pulls the bands over xGMI.
 
-Prints ONE JSON line (rank 0).  Extra keys:
-  * mrays_per_s                       closest + shadow rays per second (in-kernel counters)
+A plain run sets up, warms up, times --steps frames, writes the last timed frame's film when
+--dump-outputs DIR is given, and prints ONE JSON line (rank 0): value (Msamples/s), ms_per_step,
+mrays_per_s (closest + shadow rays per second, in-kernel counters), kernels (every kernel's HIP-event
+ms, share, launches and items in the last timed frame), build (sha256 of libyafaray4.so and its compile
+flags, yafaray_amd_buildInfo).  Everything that needs frames or CPU time of its own runs under --full
+only (the keys are null without it; --no-cpu-baseline, --no-parity and --flush-steps select among these legs):
+  * ms_per_step_flush                 frames through yafaray_render with the film flush
   * roofline                          the dominant kernel against its bound (HIP events live, per launch)
-  * kernels                           every kernel: time share, algorithmic bytes per work item
+  * kernels (the added fields)        every kernel: algorithmic bytes per work item
                                       (SURVEY §8d model), measured HBM traffic (PMC,
                                       profiles/pmc_<config>.json), achieved GB/s and fraction of 8 TB/s
   * parity                            full-size checks of this frame against the CPU oracle:
@@ -23,10 +28,9 @@ Prints ONE JSON line (rank 0).  Extra keys:
                                       image's 8x8 block means, oracle/stats.py, for two RR seeds)
                                       and an RR-off band bit for bit
   * cpu_baseline                      the oracle restatement on this host's cores, bounded band
-  * build                             sha256 of libyafaray4.so and its compile flags (yafaray_amd_buildInfo)
-  * group (N > 1)                     the library's report of the split: devices, peer-access matrix,
-                                      band copy path, band bounds, each member's render ms
-With N > 1 GPUs `parity` is group_parity's (always run): the group's frame bit for bit against a
+With N > 1 GPUs the line carries `group` (the library's report of the split: devices, peer-access matrix,
+band copy path, band bounds, each member's render ms) and `parity` is group_parity's (always run, with or
+without --full): the group's frame bit for bit against a
 one-member render, and an RR-off group frame against the oracle on rows around the band boundaries;
 the process exits with status 3 when either differs.
 """
@@ -76,7 +80,15 @@ def parse():
     ap.add_argument("--flush-steps", type=int, default=2, help="frames timed through yafaray_render with the film flush (ms_per_step_flush)")
     ap.add_argument("--members-per-gpu", type=int, default=1,
                     help="device-group members per GPU (experiment: several logical members on one GPU run on concurrent streams)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg that needs frames or CPU time of its own: the traversal-statistics frame and the "
+                         "per-kernel byte models / roofline, the flushed frames, the CPU baseline and the parity checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the film of the last timed step to DIR/film_rgba.npy and DIR/film_weights.npy (float32)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def workload_name(a, W, H):
@@ -305,9 +317,11 @@ def main():
     for _ in range(a.warmup):
         yi.render_quiet()
     # the traversal's per-visit node / triangle counters of this (deterministic) frame: one untimed
-    # frame with them, the timed frames without (yafaray_amd_setTraceStats; rays are counted always)
-    yi.render_quiet()
-    trav = {k: yi.stats()[k] for k in ("node_visits", "tri_tests")}
+    # frame with them (--full), the timed frames without (yafaray_amd_setTraceStats; rays are counted always)
+    trav = None
+    if a.full:
+        yi.render_quiet()
+        trav = {k: yi.stats()[k] for k in ("node_visits", "tri_tests")}
     yi.L.yafaray_amd_setTraceStats(yi.h, 0)
     # timed region: every launch bracketed by HIP events on the render stream (profile mode)
     yi.L.yafaray_amd_setProfileKernels(yi.h, 1)
@@ -334,11 +348,16 @@ def main():
     msps = samples_total / elapsed / 1e6
     mrays = rays_total / elapsed / 1e6
 
+    if a.dump_outputs and rank == 0:
+        # what the last timed step left in the film (the scene and the sample streams are fixed, so the
+        # same arguments give the same inputs on every run): 16 + 4 bytes per pixel, 41.5 MB at 1920x1080
+        dump_film(a.dump_outputs, *yi.film())
+
     # the reference's render() ends with the film's flush to the client (imagefilm.cc:570-670 via
     # scene.cc:203-263); renderQuiet keeps the normalised film on the GPU.  yafaray_render with a flush
     # callback (the film downloaded to the host, then the callback), timed beside the value's frames
     flush_ms = None
-    if world <= 1 and a.flush_steps > 0:
+    if a.full and world <= 1 and a.flush_steps > 0:
         yi.L.yafaray_amd_setProfileKernels(yi.h, 0)
         # one untimed flushed frame first: the host film (page-locked, reused across frames) is allocated there
         yi.render(flush=lambda: None)
@@ -350,10 +369,15 @@ def main():
         flush_ms = (time.perf_counter() - t0) / a.flush_steps * 1e3
 
     s, kt = dict(stats_acc[-1]), kt_acc[-1]
-    s.update(trav)   # node visits / triangle tests of the stats frame
-    pmc = load_pmc(a, W, H)
-    kernels, frame_ms = kernel_table(a, s, kt, pmc)
-    roof = dominant_roofline(s, kt, kernels, pmc, a.scene)
+    if a.full:
+        s.update(trav)   # node visits / triangle tests of the stats frame
+        pmc = load_pmc(a, W, H)
+        kernels, frame_ms = kernel_table(a, s, kt, pmc)
+        roof = dominant_roofline(s, kt, kernels, pmc, a.scene)
+    else:
+        # the timed frames' HIP-event times only: the byte models need the stats frame's counters
+        kernels, frame_ms = kernel_table(a, s, kt, None, models=False)
+        roof = None
 
     cpu, parity = None, None
     group = None
@@ -373,7 +397,7 @@ def main():
                               chunk=a.chunk, world=world, rank=rank, dist=dist)
         parity["check_seconds"] = round(time.perf_counter() - t_gp, 2)
         group = report
-    if rank == 0 and not grouped:
+    if a.full and rank == 0 and not grouped:
         if not a.no_cpu_baseline:
             cpu, band = cpu_baseline(spec, a)
             if not a.no_parity and band is not None:
@@ -440,14 +464,35 @@ def main():
         sys.exit(3)
 
 
-def kernel_table(a, s, kt, pmc):
-    """Per kernel kind: ms per frame, share, launches, algorithmic bytes, measured traffic, fraction."""
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_film(out_dir, rgba, w):
+    """--dump-outputs: the film as out_dir/film_rgba.npy (H, W, 4) and out_dir/film_weights.npy (H, W),
+    float32.  A film above DUMP_MAX_BYTES is written as a fixed (seeded) sample of whole pixel rows, in
+    ascending order, with the rows' numbers in out_dir/film_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    row_bytes = rgba[0].nbytes + w[0].nbytes
+    if row_bytes * rgba.shape[0] > DUMP_MAX_BYTES:
+        keep = max(1, (DUMP_MAX_BYTES - 8 * rgba.shape[0]) // row_bytes)
+        rows = np.sort(np.random.default_rng(20240607).choice(rgba.shape[0], size=keep, replace=False))
+        rgba, w = rgba[rows], w[rows]
+        np.save(os.path.join(out_dir, "film_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "film_rgba.npy"), np.ascontiguousarray(rgba, np.float32))
+    np.save(os.path.join(out_dir, "film_weights.npy"), np.ascontiguousarray(w, np.float32))
+
+
+def kernel_table(a, s, kt, pmc, models=True):
+    """Per kernel kind: ms per frame, share, launches, and (models) algorithmic bytes, measured traffic, fraction."""
     frame_ms = sum(v["ms"] for v in kt.values())
     in_lds = bool(s["scene_in_lds"])
     out = {}
     for kind, v in sorted(kt.items(), key=lambda kv: -kv[1]["ms"]):
         e = {"ms": round(v["ms"], 3), "share": round(v["ms"] / frame_ms, 4) if frame_ms else None, "launches": v["launches"],
              "items": v["items"]}
+        if not models:
+            out[kind] = e
+            continue
         ab = algo_bytes(kind, s, v, in_lds, a, kt)
         if ab is not None and v["ms"] > 0:
             e["algo_bytes_per_item"] = round(ab / max(1, v["items"]), 1)

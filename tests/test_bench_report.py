@@ -167,6 +167,33 @@ def test_fg_and_pregather_models_count_their_lookups():
     assert not _physical({"kernels": kernels})
 
 
+def test_plain_kernel_table_has_times_only():
+    """Without --full the table carries the timed frame's HIP-event figures and no byte model (the models
+    need the stats frame's counters)."""
+    kernels, frame_ms = bench.kernel_table(_args(), _stats(), _kt(), None, models=False)
+    assert abs(frame_ms - sum(v["ms"] for v in _kt().values())) < 1e-9
+    assert all(set(e) == {"ms", "share", "launches", "items"} for e in kernels.values())
+
+
+def test_dump_film_writes_float32_and_samples_rows_above_the_cap(tmp_path, monkeypatch):
+    import numpy as np
+    rng = np.random.default_rng(1)
+    rgba, w = rng.random((37, 53, 4), dtype=np.float32), rng.random((37, 53), dtype=np.float32)
+    bench.dump_film(str(tmp_path / "all"), rgba, w)
+    a, b = np.load(tmp_path / "all" / "film_rgba.npy"), np.load(tmp_path / "all" / "film_weights.npy")
+    assert a.dtype == b.dtype == np.float32 and np.array_equal(a, rgba) and np.array_equal(b, w)
+    assert not (tmp_path / "all" / "film_rows.npy").exists()
+    # a cap below the film's size: whole rows, the same ones on every call, within the cap
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 20 * 53 * 10)
+    for d in ("s1", "s2"):
+        bench.dump_film(str(tmp_path / d), rgba, w)
+    rows = np.load(tmp_path / "s1" / "film_rows.npy")
+    a, b = np.load(tmp_path / "s1" / "film_rgba.npy"), np.load(tmp_path / "s1" / "film_weights.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "film_rows.npy")) and 0 < len(rows) < 37
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, rgba[rows.astype(int)]) and np.array_equal(b, w[rows.astype(int)])
+    assert a.nbytes + b.nbytes + rows.nbytes <= 20 * 53 * 10
+
+
 def test_committed_round6_lines_are_physically_possible():
     """Every committed bench line of this round (profiles/r06_*.json, BENCH_r06.json when present)."""
     import glob
