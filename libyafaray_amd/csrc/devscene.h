@@ -370,7 +370,7 @@ struct DevPaths
 	float4 *thr;           // throughput, .w = the integrator's persistent sample weight `w`
 	float4 *col;           // col (first-vertex estimate), .w = stage | subpath << 8 | depth << 20 (bits)
 	float4 *pcol;          // path_col, .w = flags: mat_bsd_fs (v1 flags) | bits below (bits)
-	float4 *pwo;           // pwo (outgoing direction at the current path vertex): ST_FIRST entries only
+	float4 *pwo;           // pwo (outgoing direction at the current path vertex): ST_FIRST entries without F_SAMPLED only
 	float4 *pend_thr;      // throughput at the pending vertex (after Russian roulette), 12 B per entry (kernels.hip F3)
 	float4 *pend_emit;     // emission pending at that vertex
 	float4 *v0p;           // first hit p .w = prim (bits)   — only used when path_samples > 1
@@ -414,6 +414,18 @@ struct DevQueues
 	float4 *sattr;         // [2 * entries] k_surface output for the hit: (N, diffuse_refl), (diffuse colour, -)
 	const uint32_t *perm;  // ray binning (r06, BVH8 refill loop): closest entry a0 + j traces the ray of entry perm[a0 + j]
 	                       // (its segment's rays ordered by direction octant + origin Morton code); null: identity
+	// the overlapped schedule (render.cc iterate): neither changes a result
+	int trace_part;        // k_trace's plain loop: the ray kinds this launch traces (TRACE_*)
+	int nee_grid;          // k_nee workgroups (0 or >= n_seg: one per segment; fewer: a workgroup walks several segments)
+};
+
+// DevQueues::trace_part.  TRACE_CLOSEST reads no shadow count (k_nee may be writing it beside the launch);
+// TRACE_SHADOW covers [n_active, n_active + n_shadow) with the slots TRACE_BOTH gives them.
+enum : int
+{
+	TRACE_BOTH = 0,
+	TRACE_CLOSEST = 1,
+	TRACE_SHADOW = 2,
 };
 
 // Next-event-estimation requests written by k_shade, consumed by k_nee in the same iteration, and

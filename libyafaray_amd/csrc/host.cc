@@ -256,6 +256,8 @@ bool Scene::renderDeviceGroup(RenderParams &rp)
 		r.shard_y0 = rp.band_bounds[(size_t)m];
 		r.shard_y1 = rp.band_bounds[(size_t)m + 1];
 		r.pm.write_files = m == 0;
+		r.device_sharers = 0;
+		for(const GpuRenderer *g : ms) r.device_sharers += g->device() == ms[(size_t)m]->device() ? 1 : 0;
 		if(m > 0)
 		{
 			// the client's callbacks run on the caller's thread only (member 0)

@@ -1529,8 +1529,12 @@ __global__ void __launch_bounds__(kTraceBlock) YAF_TRACE_ATTR k_trace(DevScene S
 		}
 	}
 	const SegLoop L = segLoop(S.n_seg);
-	const uint32_t n_a = cnt.n_active[L.s], n_s = cnt.n_shadow[L.s];
+	// the launch's ray kinds (Q.trace_part; the plain loop below only — the refill loops and the sorted
+	// windows are launched with TRACE_BOTH).  A closest-only launch may run beside the k_nee that fills this
+	// queue's shadow rays, so it does not read their count.
+	const uint32_t n_a = cnt.n_active[L.s], n_s = Q.trace_part == TRACE_CLOSEST ? 0u : cnt.n_shadow[L.s];
 	const uint32_t total = n_a + n_s;
+	const uint32_t j_first = Q.trace_part == TRACE_SHADOW ? n_a : 0u;
 	const uint32_t a0 = L.s * S.cap_a, s0 = L.s * S.cap_s;
 	uint32_t visits = 0, tests = 0, n_closest = 0, n_shadow = 0;
 	// rays traced by traceEntry, counted per wave (ballots into scalar registers): per-lane counters
@@ -1630,7 +1634,7 @@ __global__ void __launch_bounds__(kTraceBlock) YAF_TRACE_ATTR k_trace(DevScene S
 #endif
 	// one uniform trip count per workgroup so every lane reaches the same exits (the lane's thread index
 	// re-derived per entry: threadIdx.x kept live across the traversal was spilled and reloaded per visit)
-	for(uint32_t base = L.r * blockDim.x; base < total; base += stride) countWave(traceEntry(base + (YAF_LANE_REMAT ? tidFrom(C.wave_base) : threadIdx.x)));
+	for(uint32_t base = j_first + L.r * blockDim.x; base < total; base += stride) countWave(traceEntry(base + (YAF_LANE_REMAT ? tidFrom(C.wave_base) : threadIdx.x)));
 	}
 	if(laneId() == 0)
 	{
@@ -2994,8 +2998,9 @@ __global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_SHADE_LEAN_
 			}
 			w = thr4.w;
 			flags = __float_as_uint(pcol4.w);
-			// only the first segment of a subpath reads the previous wo (path_tracer.cc:193-197)
-			if((stage & 0xffu) == ST_FIRST) pwo4 = Pc.pwo[i];
+			// only the first segment of a subpath reads the previous wo (path_tracer.cc:193-197), and only
+			// when its sample() drew nothing: a sampled segment overwrites it before any use
+			if((stage & 0xffu) == ST_FIRST && !(flags & F_SAMPLED)) pwo4 = Pc.pwo[i];
 			if(flags & F_PEND_ONE)
 			{
 				const F3 t = reinterpret_cast<const F3 *>(Pc.pend_thr)[i];
@@ -3405,7 +3410,7 @@ __global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_SHADE_LEAN_
 			if(S.w_live) stStore(&Pn.thr[k], f4(thr, w));
 			else stStoreF3(Pn.thr, k, thr);
 			stStore(&Pn.pcol[k], f4(pcol, __uint_as_float(flags)));
-			if((stage & 0xffu) == ST_FIRST) Pn.pwo[k] = f4(pwo, 0.f);
+			if((stage & 0xffu) == ST_FIRST && !(flags & F_SAMPLED)) Pn.pwo[k] = f4(pwo, 0.f);   // (the flags just stored gate the load)
 			if(nee_one) reinterpret_cast<F3 *>(Pn.pend_thr)[k] = F3{pend_thr.r, pend_thr.g, pend_thr.b};
 			if(flags & (F_PEND_EMIT | F_AO_EMIT)) Pn.pend_emit[k] = f4(emit_pend, 0.f);
 			if(keep_v0) { Pn.v0p[k] = v0p4; Pn.v0wo[k] = v0wo4; }
@@ -3886,10 +3891,12 @@ __global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_NEE_LEAN_WA
 		C.spill = nullptr;
 		C.spill_stride = 0;
 	}
-	uint32_t n_shadow = 0, n_dummy = 0, visits = 0, tests = 0;
-	// workgroup b serves the NEE requests of segment b, shadow rays go to segment b
-	const uint32_t seg = blockIdx.x;
+	// workgroup b serves the NEE requests of segment b, shadow rays go to segment b; a grid smaller than
+	// n_seg (the overlapped schedule's room for k_trace, Qn.nee_grid) walks segments b, b + grid, ..
 	__shared__ uint32_t s_count;
+	for(uint32_t seg = blockIdx.x; seg < S.n_seg; seg += gridDim.x)
+	{
+	uint32_t n_shadow = 0, n_dummy = 0, visits = 0, tests = 0;
 	if(threadIdx.x == 0) s_count = 0;
 	__syncthreads();
 	ShadeOut out;
@@ -4031,6 +4038,7 @@ __global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_NEE_LEAN_WA
 			atomicAdd(&S.stats[seg].node_visits, (unsigned long long)visits);
 			atomicAdd(&S.stats[seg].tri_tests, (unsigned long long)tests);
 		}
+	}
 	}
 }
 
@@ -7496,26 +7504,28 @@ hipError_t yafamd_launch_nee(const DevScene *S, const DevNeeQueue *N, const DevP
 	A.cnt_next = *cnt_next;
 	const size_t lds = shadeLdsBytes(*S, S->small_tables != 0);
 	A.stack_depth = stack_depth;
+	// (fewer workgroups than segments: each walks several, k_nee)
+	const int grid = (Qn->nee_grid > 0 && Qn->nee_grid < (int)S->n_seg) ? Qn->nee_grid : (int)S->n_seg;
 #ifdef YAF_EXPERIMENTS
 	if(stack_depth > 0 && yafamd_nee_trace_eligible(S, stack_depth))
 	{
-		if(S->trace_stats) hipLaunchKernelGGL((k_nee<true, false, true, true>), dim3(S->n_seg), dim3(kShadeBlock), neeTraceLdsBytes(*S, stack_depth), st, A);
-		else hipLaunchKernelGGL((k_nee<true, false, true>), dim3(S->n_seg), dim3(kShadeBlock), neeTraceLdsBytes(*S, stack_depth), st, A);
+		if(S->trace_stats) hipLaunchKernelGGL((k_nee<true, false, true, true>), dim3(grid), dim3(kShadeBlock), neeTraceLdsBytes(*S, stack_depth), st, A);
+		else hipLaunchKernelGGL((k_nee<true, false, true>), dim3(grid), dim3(kShadeBlock), neeTraceLdsBytes(*S, stack_depth), st, A);
 		return hipGetLastError();
 	}
 #endif
 	if(S->ext)
 	{
-		if(S->small_tables) hipLaunchKernelGGL((k_nee<true, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
-		else hipLaunchKernelGGL((k_nee<false, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
+		if(S->small_tables) hipLaunchKernelGGL((k_nee<true, true>), dim3(grid), dim3(kShadeBlock), lds, st, A);
+		else hipLaunchKernelGGL((k_nee<false, true>), dim3(grid), dim3(kShadeBlock), lds, st, A);
 	}
 	else if(!S->do_ao && !S->tr_shad && !S->has_mesh_light && !S->no_lean)
 	{
-		if(S->small_tables) hipLaunchKernelGGL((k_nee<true, false, false, false, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
-		else hipLaunchKernelGGL((k_nee<false, false, false, false, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
+		if(S->small_tables) hipLaunchKernelGGL((k_nee<true, false, false, false, true>), dim3(grid), dim3(kShadeBlock), lds, st, A);
+		else hipLaunchKernelGGL((k_nee<false, false, false, false, true>), dim3(grid), dim3(kShadeBlock), lds, st, A);
 	}
-	else if(S->small_tables) hipLaunchKernelGGL((k_nee<true, false>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
-	else hipLaunchKernelGGL((k_nee<false, false>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
+	else if(S->small_tables) hipLaunchKernelGGL((k_nee<true, false>), dim3(grid), dim3(kShadeBlock), lds, st, A);
+	else hipLaunchKernelGGL((k_nee<false, false>), dim3(grid), dim3(kShadeBlock), lds, st, A);
 	return hipGetLastError();
 }
 

@@ -270,6 +270,10 @@ struct GpuRenderer::Impl
 {
 	bool ok = false, init_done = false;
 	hipStream_t stream = nullptr;
+	// the overlapped schedule (render(), iterate): the closest rays of the next iteration are traced on
+	// `side` beside k_nee; ev_fork = k_shade done (main -> side), ev_join = that trace done (side -> main)
+	hipStream_t side = nullptr;
+	hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 	Buf nodes, tris, prim_ng, mats, lights, faure, faure_dim, faure_inv;
 	Buf nodes8, tris8;          // quantised BVH8 of the device-built tree and its triangles (k_trace's refill loop), or empty
 	int n_nodes8 = 0, need8 = 0, lds_top8 = 0, depth8 = 0;
@@ -365,18 +369,19 @@ struct GpuRenderer::Impl
 		}
 		return ev_pool[i];
 	}
-	int profBegin()
+	// (`st`: the stream the launch goes to; null = the render stream)
+	int profBegin(hipStream_t st = nullptr)
 	{
 		if(!prof_on) return -1;
 		hipEvent_t e = event(ev_n);
-		if(!e || hipEventRecord(e, stream) != hipSuccess) return -1;
+		if(!e || hipEventRecord(e, st ? st : stream) != hipSuccess) return -1;
 		return (int)ev_n++;
 	}
-	void profEnd(int kind, int e0)
+	void profEnd(int kind, int e0, hipStream_t st = nullptr)
 	{
 		if(e0 < 0) return;
 		hipEvent_t e = event(ev_n);
-		if(!e || hipEventRecord(e, stream) != hipSuccess) return;
+		if(!e || hipEventRecord(e, st ? st : stream) != hipSuccess) return;
 		prof_recs.push_back({kind, e0, (int)ev_n});
 		++ev_n;
 	}
@@ -413,6 +418,9 @@ struct GpuRenderer::Impl
 		yafamd_rad_grid_free(rgrid_scratch);
 		if(comm) (void)ncclCommDestroy(comm);
 		for(hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
+		if(ev_fork) (void)hipEventDestroy(ev_fork);
+		if(ev_join) (void)hipEventDestroy(ev_join);
+		if(side) (void)hipStreamDestroy(side);
 		if(stream) (void)hipStreamDestroy(stream);
 	}
 };
@@ -448,6 +456,14 @@ struct GpuRenderer::Impl
 		const int e0_ = d_->profBegin();                                                                       \
 		HIPCHECK(expr);                                                                                        \
 		d_->profEnd(kind, e0_);                                                                                \
+	} while(0)
+// the same for a launch that goes to stream `st`
+#define PROF_ON(kind, st, expr)                                                                                \
+	do                                                                                                         \
+	{                                                                                                          \
+		const int e0_ = d_->profBegin(st);                                                                     \
+		HIPCHECK(expr);                                                                                        \
+		d_->profEnd(kind, e0_, st);                                                                            \
 	} while(0)
 
 GpuRenderer::GpuRenderer(Logger &log, int device) : d_(new Impl), log_(log), device_(device) {}
@@ -503,6 +519,9 @@ bool GpuRenderer::ready()
 	if(device_ < 0) HIPCHECK(hipGetDevice(&device_));
 	DeviceGuard guard(device_);
 	HIPCHECK(hipStreamCreateWithFlags(&d_->stream, hipStreamNonBlocking));
+	HIPCHECK(hipStreamCreateWithFlags(&d_->side, hipStreamNonBlocking));
+	HIPCHECK(hipEventCreateWithFlags(&d_->ev_fork, hipEventDisableTiming));
+	HIPCHECK(hipEventCreateWithFlags(&d_->ev_join, hipEventDisableTiming));
 	int dev = device_;
 	hipDeviceProp_t prop;
 	HIPCHECK(hipGetDeviceProperties(&prop, dev));
@@ -2049,6 +2068,30 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		const char *ne = std::getenv("YAFARAY_AMD_NEE_TRACE");
 		if(yafamd_experiments() && ne && std::string(ne) == "1" && d.lds_stack >= d.stack_depth) nee_trace_stack = d.lds_stack;
 	}
+	// The overlapped schedule (YAFARAY_AMD_OVERLAP): the closest rays of iteration it + 1 depend
+	// on k_shade(it) only, so they are traced on the side stream while k_nee(it) fills the shadow queue on the
+	// render stream; the shadow rays of it + 1 follow on the render stream once both are done.  The films, the
+	// weights and the statistics are those of the serial schedule.  The render is eligible when k_trace runs its
+	// plain loop over an LDS-resident scene (the refill loops, the sorted windows and the brute-force kernel do
+	// not split by ray kind) and nothing else sits between k_shade and the next k_trace: no ray binning, no
+	// specular recursion tree, no k_tshadow / k_surface pass, no in-place NEE tracing.  Per iteration it also
+	// needs a separate k_nee launch (not the fused k_shade), no one-thread light pick (S.lpc_mode != 0: the count
+	// run, the render after it and the deferred pick's path pass stay serial), no photon-map gather kernels
+	// between k_shade and k_nee, and a next iteration.
+	// On by default with k_nee on n_seg / 2 workgroups and the closest rays on 2 n_seg (each kernel leaves the
+	// other half of the register file): C2 64.5 -> 62.4 ms per frame, the only configuration of the sweep that
+	// beat the serial schedule (profiles/c2_overlap.md).  Device-group members that share a GPU already run
+	// beside each other, and halving their k_nee grids only costs there (8 members on one GPU: 63.5 -> 68.3 ms),
+	// so they default to the serial schedule.  YAFARAY_AMD_OVERLAP=0 / 1 decides for every render; the grid
+	// variables are for sweeps.
+	bool overlap = rp.device_sharers <= 1;
+	int ov_nee_grid = std::max(1, (int)S.n_seg / 2), ov_trace_grid = std::max((int)S.n_seg, std::min(2 * (int)S.n_seg, d.trace_grid));
+	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP"); e && *e) overlap = *e != '0';
+	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_NEE_GRID"); e && atoi(e) > 0) ov_nee_grid = atoi(e);
+	// (k_trace's grid is a multiple of n_seg: segLoop)
+	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_TRACE_GRID"); e && atoi(e) > 0)
+		ov_trace_grid = (int)S.n_seg * std::max(1, std::min(atoi(e), d.trace_grid) / (int)S.n_seg);
+	overlap = overlap && S.scene_in_lds && !S.ray_sort && !S.brute && !ray_bin && !S.tree && !S.tr_shad && !S.has_attr && nee_trace_stack == 0;
 	// The megakernel (k_path, kernels.hip; opt-in YAFARAY_AMD_PATH=mega) for scenes whose BVH, stack
 	// and tables live in LDS and need none of the wavefront-only stages (EXT shading, transparent
 	// shadows, photon maps, AO): one lane per sample, the same functions in the same order, the film
@@ -2104,6 +2147,9 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		int cur = 0;
 		// a light-pick count run (S.lpc_mode 1) follows the paths only: no estimates, no shadow rays
 		const bool count_run = S.lpc_mode == 1;
+		// the overlapped schedule: this iteration's closest rays were traced on the side stream beside the
+		// previous iteration's k_nee, and the render stream has waited for them
+		bool closest_done = false;
 		for(int it = 0; it < iters; ++it)
 		{
 			// the first iteration's closest rays (camera / spawned, queue 0) carry their own (tmin, tmax);
@@ -2113,6 +2159,8 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 			if(it != 0 || (S.cur_level == 0 && !S.cam.ray_tt)) qc.ray_tt = nullptr;
 			qc.tmin_dflt = it == 0 ? 0.f : S.ray_min_dist;
 			qc.perm = nullptr;
+			qc.trace_part = closest_done ? TRACE_SHADOW : TRACE_BOTH;
+			closest_done = false;
 			if(ray_bin && it >= 1 && !count_run)
 			{
 				// the bounce rays ordered by direction octant + origin (camera rays are coherent already)
@@ -2172,7 +2220,40 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 			}
 			// NEE requests (none in iteration 1 of photon mapping, whose entries all finish there)
 			if(!yafamd_shade_fused_for(&S) && !(S.integrator == INT_PHOTON && it == 1) && !count_run)
-				PROF(KK_NEE, yafamd_launch_nee(&S, &d.N, &d.P[cur ^ 1], &d.Q[cur ^ 1], &cnt[cur ^ 1], nee_trace_stack, d.stream));
+			{
+				if(overlap && S.lpc_mode == 0 && !S.gather_on && it + 1 < iters)
+				{
+					// k_shade(it) is queued: the next iteration's closest rays go to the side stream, k_nee(it)
+					// beside them to the render stream, which then waits for the side stream — so nothing of
+					// the side stream is pending when this iteration's launches end (chunk buffers, the next
+					// pass and the render's final synchronisation see one stream, as before)
+					DevQueues qn = d.Q[cur ^ 1];
+					qn.ray_tt = nullptr;
+					qn.tmin_dflt = S.ray_min_dist;
+					qn.perm = nullptr;
+					qn.trace_part = TRACE_CLOSEST;
+					DevQueues qnee = d.Q[cur ^ 1];
+					qnee.nee_grid = ov_nee_grid;
+					HIPCHECK(hipEventRecord(d.ev_fork, d.stream));
+					HIPCHECK(hipStreamWaitEvent(d.side, d.ev_fork, 0));
+					bool ok = [&]() -> bool {
+						PROF_ON(KK_TRACE, d.side, yafamd_launch_trace(&S, &qn, &cnt[cur ^ 1], &d.P[cur ^ 1], run_stats, d.lds_stack, (int *)d.spill.p,
+						                                              ov_trace_grid, d.side));
+						HIPCHECK(hipEventRecord(d.ev_join, d.side));
+						PROF(KK_NEE, yafamd_launch_nee(&S, &d.N, &d.P[cur ^ 1], &qnee, &cnt[cur ^ 1], nee_trace_stack, d.stream));
+						HIPCHECK(hipStreamWaitEvent(d.stream, d.ev_join, 0));
+						return true;
+					}();
+					if(!ok)
+					{
+						(void)hipStreamSynchronize(d.side);   // a failed launch: leave no side-stream work behind
+						return false;
+					}
+					closest_done = true;
+				}
+				else
+					PROF(KK_NEE, yafamd_launch_nee(&S, &d.N, &d.P[cur ^ 1], &d.Q[cur ^ 1], &cnt[cur ^ 1], nee_trace_stack, d.stream));
+			}
 			// (non-EXT k_shade runs the NEE itself: FUSED)
 			cur ^= 1;
 		}

@@ -119,6 +119,7 @@ struct RenderParams
 	                      // 2: the explicit band [shard_y0, shard_y1) (host-side load balancing)
 	int shard_y0 = 0, shard_y1 = 0;
 	int chunk_slots = 1 << 27;   // samples in flight per wavefront chunk (134 M: the C2 frame in one chunk)
+	int device_sharers = 1;      // device-group members of this process rendering on this member's GPU (itself included)
 	bool profile = false;
 	// film load/save (filmio.h): accumulators loaded from film files, uploaded before the first pass;
 	// resumed = the first pass renders no samples (integrator_tiled.cc:174-177)
