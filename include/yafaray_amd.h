@@ -93,6 +93,14 @@ YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_buildAccelerator(yafaray_Interfa
 YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_traceClosest(yafaray_Interface_t *interface, const float *rays, int n, float *t, int *prims);
 YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_traceShadow(yafaray_Interface_t *interface, const float *rays, int n, int *occluded);
 
+/* The built scene's primitives [first, first + count) in creation order (instances expanded, as the
+ * ray queries number them), as the device holds them: verts9 the three world-space vertices, ng3 the
+ * geometric normal, vnormals9 the three vertex normals (the geometric normal where the primitive is
+ * not smooth), material the material's creation index.  Any output may be NULL.  Builds the scene if
+ * it is dirty; count = 0 with every output NULL only builds.  Returns the scene's primitive count,
+ * -1 on failure. */
+YAFARAY_C_API_EXPORT int yafaray_amd_getPrimitives(yafaray_Interface_t *interface, int first, int count, float *verts9, float *ng3, float *vnormals9, int *material);
+
 /* Film of the last render: rgba width*height*4 floats (normalised, = put-pixel values), weights width*height. */
 YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_getFilm(const yafaray_Interface_t *interface, float *rgba, float *weights);
 /* Film straight into device memory (rows [y0, y1) of a width*height*4 float buffer on the render device). */

@@ -90,6 +90,11 @@ def lib():
             "yafaray_addUv": (i, [vp, f, f]),
             "yafaray_addNormal": (None, [vp, d, d, d]),
             "yafaray_smoothMesh": (b, [vp, cp, d]),
+            "yafaray_addInstance": (b, [vp, cp] + [f] * 16),
+            "yafaray_addInstanceArray": (b, [vp, cp, C.POINTER(C.c_float)]),
+            "yafaray_amd_getPrimitives": (i, [vp, i, i, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+            "yafaray_clearAll": (None, [vp]),
+            "yafaray_getNextFreeId": (C.c_uint, [vp]),
             "yafaray_createImage": (vp, [vp, cp]),
             "yafaray_setImageColor": (b, [vp, i, i, f, f, f, f]),
             "yafaray_getImageColor": (b, [vp, i, i, C.POINTER(f), C.POINTER(f), C.POINTER(f), C.POINTER(f)]),
@@ -163,7 +168,8 @@ def lib():
             "yafaray_amd_getKernelTimes": (i, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_uint64),
                                                C.POINTER(C.c_uint64), i]),
         }
-        optional = {"yafaray_amd_buildInfo", "yafaray_amd_getGroupReport"}   # LIBYAFARAY_AMD_1.4 (variant builds of older sources lack them)
+        # LIBYAFARAY_AMD_1.4 / 1.7 (variant builds of older sources lack them)
+        optional = {"yafaray_amd_buildInfo", "yafaray_amd_getGroupReport", "yafaray_amd_getPrimitives"}
         for name, (res, args) in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -247,6 +253,39 @@ class Interface:
         a = np.ascontiguousarray(abc, np.int32).reshape(-1)
         if not self.L.yafaray_amd_addTriangles(self.h, a.ctypes.data_as(C.POINTER(C.c_int)), len(a) // 3):
             raise RuntimeError(self.last_error())
+
+    # --- object instances ---
+    def addInstance(self, base_name, m):
+        """yafaray_addInstance: `m` is obj_to_world, (3, 4) or (4, 4) row-major (row 3 is never read)."""
+        m = np.asarray(m, np.float32)
+        if m.shape == (3, 4):
+            m = np.concatenate([m, np.asarray([[0, 0, 0, 1]], np.float32)])
+        return bool(self.L.yafaray_addInstance(self.h, _b(base_name), *[float(x) for x in m.reshape(16)]))
+
+    def addInstanceArray(self, base_name, m):
+        """yafaray_addInstanceArray: the same through a float[4][4]."""
+        m = np.ascontiguousarray(m, np.float32)
+        if m.shape == (3, 4):
+            m = np.ascontiguousarray(np.concatenate([m, np.asarray([[0, 0, 0, 1]], np.float32)]))
+        return bool(self.L.yafaray_addInstanceArray(self.h, _b(base_name), m.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def primitives(self, first=0, count=None):
+        """The built scene's primitives [first, first + count) as the device holds them (yafaray_amd_getPrimitives):
+        {"verts": (n, 3, 3), "ng": (n, 3), "vnormals": (n, 3, 3), "material": (n,)}.  count None: to the end."""
+        fp = C.POINTER(C.c_float)
+        if count is None:
+            total = self.L.yafaray_amd_getPrimitives(self.h, 0, 0, None, None, None, None)
+            if total < 0:
+                raise RuntimeError("getPrimitives failed: " + self.last_error())
+            count = total - first
+        v = np.empty((count, 3, 3), np.float32)
+        ng = np.empty((count, 3), np.float32)
+        vn = np.empty((count, 3, 3), np.float32)
+        mat = np.empty(count, np.int32)
+        if self.L.yafaray_amd_getPrimitives(self.h, int(first), int(count), v.ctypes.data_as(fp), ng.ctypes.data_as(fp),
+                                            vn.ctypes.data_as(fp), mat.ctypes.data_as(C.POINTER(C.c_int))) < 0:
+            raise RuntimeError("getPrimitives failed: " + self.last_error())
+        return {"verts": v, "ng": ng, "vnormals": vn, "material": mat}
 
     def last_error(self) -> str:
         e = self.L.yafaray_amd_lastError(self.h)

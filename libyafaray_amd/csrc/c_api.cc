@@ -73,7 +73,7 @@ yafaray_bool_t yafaray_endGeometry(yafaray_Interface_t *interface) { return I(in
 unsigned int yafaray_getNextFreeId(yafaray_Interface_t *interface)
 {
 	Scene *s = I(interface)->sc();
-	return s ? (unsigned int)s->objects.size() + 1 : 0;
+	return s ? (unsigned int)(s->objects.size() + s->instances.size()) + 1 : 0;
 }
 
 yafaray_bool_t yafaray_endObject(yafaray_Interface_t *interface)
@@ -124,16 +124,18 @@ yafaray_bool_t yafaray_smoothMesh(yafaray_Interface_t *interface, const char *na
 	return (s && s->smoothMesh(name ? name : "", (float)angle)) ? YAFARAY_BOOL_TRUE : YAFARAY_BOOL_FALSE;
 }
 
-yafaray_bool_t yafaray_addInstance(yafaray_Interface_t *interface, const char *base_object_name, float, float, float, float, float, float, float, float, float, float, float, float, float, float, float, float)
+// interface.cc:108-116 (the matrix row by row) -> Scene::addInstance
+yafaray_bool_t yafaray_addInstance(yafaray_Interface_t *interface, const char *base_object_name, float m_00, float m_01, float m_02, float m_03, float m_10, float m_11, float m_12, float m_13, float m_20, float m_21, float m_22, float m_23, float m_30, float m_31, float m_32, float m_33)
 {
-	I(interface)->logger.error(std::string("Scene: instances ('") + (base_object_name ? base_object_name : "") + "') are not supported by the GPU core yet");
-	return YAFARAY_BOOL_FALSE;
+	Scene *s = I(interface)->sc();
+	const float m[16] = {m_00, m_01, m_02, m_03, m_10, m_11, m_12, m_13, m_20, m_21, m_22, m_23, m_30, m_31, m_32, m_33};
+	return (s && s->addInstance(base_object_name ? base_object_name : "", m)) ? YAFARAY_BOOL_TRUE : YAFARAY_BOOL_FALSE;
 }
 
 yafaray_bool_t yafaray_addInstanceArray(yafaray_Interface_t *interface, const char *base_object_name, const float obj_to_world[4][4])
 {
-	(void)obj_to_world;
-	return yafaray_addInstance(interface, base_object_name, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0);
+	Scene *s = I(interface)->sc();
+	return (s && obj_to_world && s->addInstance(base_object_name ? base_object_name : "", &obj_to_world[0][0])) ? YAFARAY_BOOL_TRUE : YAFARAY_BOOL_FALSE;
 }
 
 // ---- params (interface.cc:118-172) ----
@@ -480,6 +482,13 @@ yafaray_bool_t yafaray_amd_traceClosest(yafaray_Interface_t *interface, const fl
 	if(!s) return YAFARAY_BOOL_FALSE;
 	if(s->geometry_dirty && !s->buildAccelerator()) return YAFARAY_BOOL_FALSE;
 	return s->gpu()->traceRays(false, rays, n, t, prims) ? YAFARAY_BOOL_TRUE : YAFARAY_BOOL_FALSE;
+}
+
+int yafaray_amd_getPrimitives(yafaray_Interface_t *interface, int first, int count, float *verts9, float *ng3, float *vnormals9, int *material)
+{
+	Scene *s = I(interface)->sc();
+	if(!s || !s->getPrimitives(first, count, verts9, ng3, vnormals9, material)) return -1;
+	return s->gpu()->primitiveCount();
 }
 
 yafaray_bool_t yafaray_amd_traceShadow(yafaray_Interface_t *interface, const float *rays, int n, int *occluded)

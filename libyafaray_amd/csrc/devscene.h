@@ -133,9 +133,28 @@ struct DevNode
 //   [0] v0 (.w = flags ATTR_*)  [1] e1  [2] e2          Moller-Trumbore operands (barycentrics)
 //   [3..5] orco vertices        [6] (u0, v0, u1, v1)  [7] (u2, v2, -, -)
 //   [8..10] vertex normals (smooth / exported normals; face normal where a vertex has none)
+// An instance's primitive without orco keeps its base's geometric normal in [3] (ATTR_BASE_NG): the
+// orco normal is the base's, untransformed (primitive_triangle.cc:114-127).
 constexpr int kAttrF4 = 11;
 constexpr int kMaxNodes = 16;   // shader nodes per material program
-enum : uint32_t { ATTR_ORCO = 1u, ATTR_UV = 2u, ATTR_SMOOTH = 4u };
+enum : uint32_t { ATTR_ORCO = 1u, ATTR_UV = 2u, ATTR_SMOOTH = 4u, ATTR_BASE_NG = 8u };
+// Only in the source rows the instance expansion reads (instexpand.hip), never in DevScene::prim_attr:
+// vertex r of the primitive has no normal of its own, the expansion writes the instance's face normal
+enum : uint32_t { ATTR_SRC_FACE_N0 = 1u << 8, ATTR_SRC_MASK = 7u << 8 };
+
+// One run of output primitives of a scene with instances (instexpand.hip): a visible plain mesh
+// (identity: its rows are copied bit for bit) or an ObjectInstance (object_instance.h:28-60: every
+// base primitive under obj_to_world).  Source ranges index the once-uploaded object-space rows,
+// output offsets the world-space arrays the renderer consumes; both grow with the segment index.
+struct DevInstSeg
+{
+	float m[12];              // rows 0..2 of obj_to_world, row-major (row 3 is never read, matrix4.h:78-90)
+	int src_vert0, n_verts;
+	int src_prim0, n_prims;
+	int out_vert0, out_prim0;
+	uint32_t identity;
+	uint32_t pad;
+};
 
 struct DevLight
 {

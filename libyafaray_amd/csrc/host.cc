@@ -1006,6 +1006,11 @@ bool Scene::setupRender(const ParamMap &p)
 bool Scene::meshLightFaces(const std::string &name, DevLight &L, HostScene &hs)
 {
 	auto lo = light_objects.find(name);
+	if(lo != light_objects.end() && instances.count(lo->second))
+	{
+		log.error("Light '" + name + "': object '" + lo->second + "' is an instance; instanced mesh lights are not supported by the GPU core");
+		return false;
+	}
 	auto it = lo == light_objects.end() ? objects.end() : objects.find(lo->second);
 	if(it == objects.end() || it->second.tri_mat.empty())
 	{
@@ -1069,9 +1074,264 @@ bool Scene::meshLightFaces(const std::string &name, DevLight &L, HostScene &hs)
 	return true;
 }
 
+// One primitive's surface attribute rows (texeval.h surfAttr; primitive_triangle.cc:97-176); ng: its
+// prim_ng row, a: kAttrF4 zeroed float4.  src: a source row of the instance expansion (instexpand.hip):
+// a vertex without a normal of its own is marked, the expansion writes the instance's face normal there.
+static void attrRows(const MeshObject &o, size_t k, const float *ng, float *a, bool src)
+{
+	const bool has_orco = !o.orco.empty(), has_uv = !o.uvs.empty(), smooth = o.smooth || !o.normals.empty();
+	const size_t nn = o.normals.size() / 3;
+	const int *vi = &o.tris[3 * k];
+	const F3 p0 = f3(&o.verts[3 * (size_t)vi[0]]), p1 = f3(&o.verts[3 * (size_t)vi[1]]), p2 = f3(&o.verts[3 * (size_t)vi[2]]);
+	uint32_t fl = 0;
+	put(a + 4, sub(p1, p0));
+	put(a + 8, sub(p2, p0));
+	if(has_orco && o.orco.size() >= 3 * (o.verts.size() / 3))
+	{
+		fl |= ATTR_ORCO;
+		for(int r = 0; r < 3; ++r) put(a + 12 + 4 * r, f3(&o.orco[3 * (size_t)vi[r]]));
+	}
+	const int *ui = o.tri_uv.size() >= 3 * (k + 1) ? &o.tri_uv[3 * k] : nullptr;
+	if(has_uv && ui && ui[0] >= 0 && ui[1] >= 0 && ui[2] >= 0)
+	{
+		const float *u0 = &o.uvs[2 * (size_t)ui[0]], *u1 = &o.uvs[2 * (size_t)ui[1]], *u2 = &o.uvs[2 * (size_t)ui[2]];
+		const float du_1 = u1[0] - u0[0], du_2 = u2[0] - u0[0], dv_1 = u1[1] - u0[1], dv_2 = u2[1] - u0[1];
+		const float det = du_1 * dv_2 - dv_1 * du_2;
+		if(std::abs(det) > 1e-30f) fl |= ATTR_UV;   // else implicit uv (:144-152)
+		a[24] = u0[0]; a[25] = u0[1]; a[26] = u1[0]; a[27] = u1[1];
+		a[28] = u2[0]; a[29] = u2[1];
+	}
+	if(smooth)
+	{
+		fl |= ATTR_SMOOTH;
+		for(int r = 0; r < 3; ++r)
+		{
+			const int ni = o.tri_nidx.size() >= 3 * (k + 1) ? o.tri_nidx[3 * k + r] : -1;
+			if(ni >= 0 && (size_t)ni < nn) put(a + 32 + 4 * r, f3(&o.normals[3 * (size_t)ni]));
+			else
+			{
+				put(a + 32 + 4 * r, F3{ng[0], ng[1], ng[2]});   // getVertexNormal: face normal
+				if(src) fl |= ATTR_SRC_FACE_N0 << r;
+			}
+		}
+	}
+	float flf;
+	std::memcpy(&flf, &fl, 4);
+	put(a, p0, flf);
+}
+
+// scene.cc:1013-1030.  The instance takes its place in object_order now; its base is looked up again
+// when the scene is built.
+bool Scene::addInstance(const std::string &base_object_name, const float m[16])
+{
+	if(instances.count(base_object_name))
+	{
+		log.error("Scene: the base '" + base_object_name + "' of an instance is itself an instance, which the GPU core does not support");
+		return false;
+	}
+	if(!objects.count(base_object_name))
+	{
+		log.error("Base mesh for instance doesn't exist " + base_object_name);
+		return false;
+	}
+	size_t id = objects.size() + instances.size() + 1;   // getNextFreeId
+	std::string name = base_object_name + "-" + std::to_string(id);
+	while(objects.count(name) || instances.count(name)) name = base_object_name + "-" + std::to_string(++id);
+	InstanceDesc &in = instances[name];
+	in.base = base_object_name;
+	std::memcpy(in.m, m, sizeof(in.m));
+	object_order.push_back(name);
+	geometry_dirty = true;
+	return true;
+}
+
+// The scene with instances (scene.cc:1032-1060 updateObjects over meshes and ObjectInstances): the
+// source rows of every mesh that shows — itself or through an instance — once, and the segments in
+// object order.  An instance has its base's visibility and is never a base object
+// (object_instance.h:44-46); its primitives come in the base's order.
+bool Scene::gatherInstanced(HostScene &hs)
+{
+	struct Src { int vert0, prim0; };
+	std::map<std::string, Src> placed;
+	std::vector<std::pair<const MeshObject *, int>> sources;   // and their first source primitive
+	hs.instanced = true;
+	int64_t out_verts = 0, out_prims = 0;
+	for(const std::string &name : object_order)
+	{
+		auto ii = instances.find(name);
+		auto oi = objects.find(ii == instances.end() ? name : ii->second.base);
+		if(oi == objects.end())
+		{
+			log.error("Base mesh for instance doesn't exist " + (ii == instances.end() ? name : ii->second.base));
+			return false;
+		}
+		const MeshObject &o = oi->second;
+		if(o.visibility == "invisible" || (ii == instances.end() && o.is_base) || o.tri_mat.empty()) continue;
+		auto pi = placed.find(o.name);
+		if(pi == placed.end())
+		{
+			pi = placed.emplace(o.name, Src{(int)(hs.verts.size() / 3), (int)(hs.prim_ng.size() / 4)}).first;
+			hs.verts.insert(hs.verts.end(), o.verts.begin(), o.verts.end());
+			hs.tris.insert(hs.tris.end(), o.tris.begin(), o.tris.end());
+			for(size_t t = 0; t < o.tri_mat.size(); ++t)
+			{
+				// primitive_triangle.cc:87-95 geometric normal; material index per primitive
+				const F3 a = f3(&o.verts[3 * (size_t)o.tris[3 * t]]), b = f3(&o.verts[3 * (size_t)o.tris[3 * t + 1]]), c = f3(&o.verts[3 * (size_t)o.tris[3 * t + 2]]);
+				float row[4], matf;
+				std::memcpy(&matf, &o.tri_mat[t], 4);
+				put(row, nrm(crs(sub(b, a), sub(c, a))), matf);
+				hs.prim_ng.insert(hs.prim_ng.end(), row, row + 4);
+			}
+			if(o.smooth || !o.normals.empty()) hs.has_attr = true;
+			sources.emplace_back(&o, pi->second.prim0);
+		}
+		DevInstSeg g{};
+		if(ii != instances.end()) std::memcpy(g.m, ii->second.m, sizeof(g.m));
+		g.identity = ii == instances.end() ? 1u : 0u;
+		g.src_vert0 = pi->second.vert0;
+		g.n_verts = (int)(o.verts.size() / 3);
+		g.src_prim0 = pi->second.prim0;
+		g.n_prims = (int)o.tri_mat.size();
+		g.out_vert0 = (int)out_verts;
+		g.out_prim0 = (int)out_prims;
+		out_verts += g.n_verts;
+		out_prims += g.n_prims;
+		// the device arrays are indexed with int (3 indices per primitive, 3 floats per vertex)
+		if(3 * out_verts > INT_MAX || 3 * out_prims > INT_MAX)
+		{
+			log.error("Scene: the instances expand to more than " + std::to_string(INT_MAX / 3) + " primitives or vertices, which the GPU core's arrays cannot index");
+			return false;
+		}
+		hs.segs.push_back(g);
+	}
+	hs.n_verts = (int)out_verts;
+	hs.n_prims = (int)out_prims;
+	if(hs.has_attr)
+	{
+		hs.prim_attr.assign(hs.prim_ng.size() / 4 * kAttrF4 * 4, 0.f);
+		for(const auto &so : sources)
+			for(size_t k = 0; k < so.first->tri_mat.size(); ++k)
+				attrRows(*so.first, k, &hs.prim_ng[4 * ((size_t)so.second + k)], &hs.prim_attr[((size_t)so.second + k) * kAttrF4 * 4], true);
+	}
+	return true;
+}
+
+bool Scene::getPrimitives(int first, int count, float *verts9, float *ng3, float *vnormals9, int *material)
+{
+	if(geometry_dirty && !buildAccelerator()) return false;
+	GpuRenderer *g = gpu();
+	if(g->hasWorldVerts() || !verts9) return g->readPrimitives(first, count, verts9, ng3, vnormals9, material);
+	// a scene without instances: the device keeps no vertex array (its BVH's triangle records hold the
+	// vertices); the world-space vertices are the objects' own
+	if(!g->readPrimitives(first, count, nullptr, ng3, vnormals9, material)) return false;
+	int64_t t = 0;
+	for(const std::string &name : object_order)
+	{
+		const MeshObject &o = objects[name];
+		if(o.is_base || o.visibility == "invisible") continue;
+		for(size_t k = 0; k < o.tri_mat.size(); ++k, ++t)
+		{
+			if(t < first || t >= (int64_t)first + count) continue;
+			for(int r = 0; r < 3; ++r) std::memcpy(verts9 + 9 * (t - first) + 3 * r, &o.verts[3 * (size_t)o.tris[3 * k + (size_t)r]], 12);
+		}
+	}
+	return true;
+}
+
+// the materials in creation order with their shader-node programs, and the image textures
+void Scene::materialRows(HostScene &hs)
+{
+	for(const std::string &mn : material_order)
+	{
+		DevMaterial m = materials[mn];
+		auto nit = mat_nodes.find(mn);
+		m.node0 = (int)hs.shader_nodes.size();
+		if(nit != mat_nodes.end()) hs.shader_nodes.insert(hs.shader_nodes.end(), nit->second.begin(), nit->second.end());
+		else m.n_nodes = 0;
+		if(m.n_nodes > 0) hs.has_attr = true;
+		hs.mats.push_back(m);
+	}
+	if(hs.mats.empty()) hs.mats.push_back(DevMaterial{});
+	// image textures: texels = the image buffers' getColor() values (one copy per image)
+	{
+		std::map<const HostImage *, uint32_t> placed;
+		for(const HostTexture &ht : textures)
+		{
+			DevTexture t = ht.t;
+			auto pit = placed.find(ht.img.get());
+			if(pit == placed.end())
+			{
+				const uint32_t off = (uint32_t)(hs.texels.size() / 4);
+				hs.texels.insert(hs.texels.end(), ht.img->px.begin(), ht.img->px.end());
+				pit = placed.emplace(ht.img.get(), off).first;
+			}
+			t.texel0 = pit->second;
+			hs.textures.push_back(t);
+		}
+	}
+}
+
+bool Scene::lightsAndUpload(HostScene &hs)
+{
+	// the visible lights in name order (render_view.cc:83-91: the integrators' list), then the photon-only
+	// ones (only the photon maps' light sets refer to them)
+	{
+		std::map<std::string, int> at;
+		for(int pass = 0; pass < 2; ++pass)
+			for(auto &kv : lights)
+			{
+				DevLight L = kv.second;
+				if((L.photon_only != 0) != (pass == 1)) continue;
+				if(L.type == LIGHT_MESH && !meshLightFaces(kv.first, L, hs)) return false;
+				at[kv.first] = (int)hs.lights.size();
+				hs.lights.push_back(L);
+			}
+		for(const auto &kv : at) hs.light_name_order.push_back(kv.second);
+	}
+	uint32_t base = 0;
+	for(DevLight &L : hs.lights) { L.nee_base = base; base += L.nee_count; }
+	for(int m = 0; m < memberCount(); ++m)
+		if(!member(m)->upload(hs)) return false;
+	return true;
+}
+
 bool Scene::buildAccelerator()
 {
 	if(!syncMembers()) return false;
+	if(!instances.empty())
+	{
+		const auto t0 = std::chrono::steady_clock::now();
+		HostScene hs;
+		materialRows(hs);   // (has_attr: a material with shader nodes)
+		if(!gatherInstanced(hs)) return false;
+		int leaf = 1, width = 4;
+		float node_cost = 0.f;
+		if(const char *e = getenv("YAFARAY_AMD_BVH_LEAF")) leaf = std::max(1, atoi(e));
+		if(const char *e = getenv("YAFARAY_AMD_BVH_NODE_COST")) node_cost = (float)atof(e);
+		if(const char *e = getenv("YAFARAY_AMD_BVH_WIDTH")) width = atoi(e) == 2 ? 2 : 4;
+		hs.gpu_build = width == 4 && hs.n_prims >= 65536;
+		if(const char *e = getenv("YAFARAY_AMD_BVH_BUILD"); e && *e) hs.gpu_build = width == 4 && std::string(e) == "gpu";
+		if(!hs.gpu_build)
+		{
+			// the host's SAH builder needs world vertices: member 0 expands, the vertices and indices come back
+			std::vector<float> verts;
+			std::vector<int> tris;
+			if(!gpu()->expandInstances(hs, &verts, &tris)) return false;
+			BvhInput in{verts.data(), tris.data(), hs.n_prims};
+			if(node_cost > 0.f) in.node_cost = node_cost;
+			in.width = width;
+			hs.bvh = buildBvh(in, leaf, 8);
+		}
+		if(!lightsAndUpload(hs)) return false;
+		stats.build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+		std::ostringstream os;
+		os << "Accelerator: BVH" << hs.bvh.width << (hs.gpu_build ? " (built on the GPU: PLOC + collapse)" : " (binned SAH on the host)") << " over " << hs.n_prims
+		   << " triangles (" << instances.size() << " instances expanded on the GPU): " << hs.bvh.n_nodes << " nodes, depth " << hs.bvh.depth << ", max leaf "
+		   << hs.bvh.max_leaf << " (" << stats.build_seconds << " s)";
+		log.info(os.str());
+		geometry_dirty = false;
+		return true;
+	}
 	// scene.cc:1032-1060 updateObjects: gather visible, non-base mesh primitives
 	std::vector<float> verts;
 	std::vector<int> tris, tri_mat;
@@ -1117,34 +1377,7 @@ bool Scene::buildAccelerator()
 		std::memcpy(&matf, &tri_mat[t], 4);
 		put(&hs.prim_ng[4 * (size_t)t], n, matf);
 	}
-	for(const std::string &mn : material_order)
-	{
-		DevMaterial m = materials[mn];
-		auto nit = mat_nodes.find(mn);
-		m.node0 = (int)hs.shader_nodes.size();
-		if(nit != mat_nodes.end()) hs.shader_nodes.insert(hs.shader_nodes.end(), nit->second.begin(), nit->second.end());
-		else m.n_nodes = 0;
-		if(m.n_nodes > 0) hs.has_attr = true;
-		hs.mats.push_back(m);
-	}
-	if(hs.mats.empty()) hs.mats.push_back(DevMaterial{});
-	// image textures: texels = the image buffers' getColor() values (one copy per image)
-	{
-		std::map<const HostImage *, uint32_t> placed;
-		for(const HostTexture &ht : textures)
-		{
-			DevTexture t = ht.t;
-			auto pit = placed.find(ht.img.get());
-			if(pit == placed.end())
-			{
-				const uint32_t off = (uint32_t)(hs.texels.size() / 4);
-				hs.texels.insert(hs.texels.end(), ht.img->px.begin(), ht.img->px.end());
-				pit = placed.emplace(ht.img.get(), off).first;
-			}
-			t.texel0 = pit->second;
-			hs.textures.push_back(t);
-		}
-	}
+	materialRows(hs);
 	for(const std::string &name : object_order)
 	{
 		const MeshObject &o = objects[name];
@@ -1160,67 +1393,11 @@ bool Scene::buildAccelerator()
 		{
 			const MeshObject &o = objects[name];
 			if(o.is_base || o.visibility == "invisible") continue;
-			const bool has_orco = !o.orco.empty(), has_uv = !o.uvs.empty(), smooth = o.smooth || !o.normals.empty();
-			const size_t nn = o.normals.size() / 3;
 			for(size_t k = 0; k < o.tri_mat.size(); ++k, ++t)
-			{
-				float *a = &hs.prim_attr[(size_t)t * kAttrF4 * 4];
-				const int *vi = &o.tris[3 * k];
-				const F3 p0 = f3(&o.verts[3 * (size_t)vi[0]]), p1 = f3(&o.verts[3 * (size_t)vi[1]]), p2 = f3(&o.verts[3 * (size_t)vi[2]]);
-				uint32_t fl = 0;
-				put(a + 4, sub(p1, p0));
-				put(a + 8, sub(p2, p0));
-				if(has_orco && o.orco.size() >= 3 * (o.verts.size() / 3))
-				{
-					fl |= ATTR_ORCO;
-					for(int r = 0; r < 3; ++r) put(a + 12 + 4 * r, f3(&o.orco[3 * (size_t)vi[r]]));
-				}
-				const int *ui = o.tri_uv.size() >= 3 * (k + 1) ? &o.tri_uv[3 * k] : nullptr;
-				if(has_uv && ui && ui[0] >= 0 && ui[1] >= 0 && ui[2] >= 0)
-				{
-					const float *u0 = &o.uvs[2 * (size_t)ui[0]], *u1 = &o.uvs[2 * (size_t)ui[1]], *u2 = &o.uvs[2 * (size_t)ui[2]];
-					const float du_1 = u1[0] - u0[0], du_2 = u2[0] - u0[0], dv_1 = u1[1] - u0[1], dv_2 = u2[1] - u0[1];
-					const float det = du_1 * dv_2 - dv_1 * du_2;
-					if(std::abs(det) > 1e-30f) fl |= ATTR_UV;   // else implicit uv (:144-152)
-					a[24] = u0[0]; a[25] = u0[1]; a[26] = u1[0]; a[27] = u1[1];
-					a[28] = u2[0]; a[29] = u2[1];
-				}
-				if(smooth)
-				{
-					fl |= ATTR_SMOOTH;
-					const float *ng = &hs.prim_ng[4 * (size_t)t];
-					for(int r = 0; r < 3; ++r)
-					{
-						const int ni = o.tri_nidx.size() >= 3 * (k + 1) ? o.tri_nidx[3 * k + r] : -1;
-						if(ni >= 0 && (size_t)ni < nn) put(a + 32 + 4 * r, f3(&o.normals[3 * (size_t)ni]));
-						else put(a + 32 + 4 * r, F3{ng[0], ng[1], ng[2]});   // getVertexNormal: face normal
-					}
-				}
-				float flf;
-				std::memcpy(&flf, &fl, 4);
-				put(a, p0, flf);
-			}
+				attrRows(o, k, &hs.prim_ng[4 * (size_t)t], &hs.prim_attr[(size_t)t * kAttrF4 * 4], false);
 		}
 	}
-	// the visible lights in name order (render_view.cc:83-91: the integrators' list), then the photon-only
-	// ones (only the photon maps' light sets refer to them)
-	{
-		std::map<std::string, int> at;
-		for(int pass = 0; pass < 2; ++pass)
-			for(auto &kv : lights)
-			{
-				DevLight L = kv.second;
-				if((L.photon_only != 0) != (pass == 1)) continue;
-				if(L.type == LIGHT_MESH && !meshLightFaces(kv.first, L, hs)) return false;
-				at[kv.first] = (int)hs.lights.size();
-				hs.lights.push_back(L);
-			}
-		for(const auto &kv : at) hs.light_name_order.push_back(kv.second);
-	}
-	uint32_t base = 0;
-	for(DevLight &L : hs.lights) { L.nee_base = base; base += L.nee_count; }
-	for(int m = 0; m < memberCount(); ++m)
-		if(!member(m)->upload(hs)) return false;
+	if(!lightsAndUpload(hs)) return false;
 	const auto t1 = std::chrono::steady_clock::now();
 	stats.build_seconds = std::chrono::duration<double>(t1 - t0).count();
 	std::ostringstream os;

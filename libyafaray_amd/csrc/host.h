@@ -124,6 +124,15 @@ struct MeshObject
 	bool ended = false;
 };
 
+// ObjectInstance (object_instance.h:28-60): every primitive of `base` under obj_to_world.  The base is
+// referred to by name and resolved when the scene is built (the reference's instance holds a reference
+// to the base object, so later changes of the base show).
+struct InstanceDesc
+{
+	std::string base;
+	float m[12];   // rows 0..2 of obj_to_world, row-major
+};
+
 struct CameraDesc
 {
 	float from[3] = {0.f, 1.f, 0.f}, to[3] = {0.f, 0.f, 0.f}, up[3] = {0.f, 1.f, 1.f};
@@ -200,7 +209,8 @@ class Scene
 		std::map<std::string, DevLight> lights;        // std::map: name order (render_view.cc:61)
 		std::map<std::string, std::string> light_objects;   // meshlight / objectlight -> its object (resolved when the scene is built)
 		std::map<std::string, MeshObject> objects;
-		std::vector<std::string> object_order;
+		std::map<std::string, InstanceDesc> instances;   // named <base>-<id> (scene.cc:1021-1026)
+		std::vector<std::string> object_order;           // mesh objects and instances in creation order
 		std::map<std::string, CameraDesc> cameras;
 		std::map<std::string, std::string> views;     // view name -> camera name
 		std::map<std::string, std::vector<float>> backgrounds;   // colour * power
@@ -240,6 +250,9 @@ class Scene
 		int addUv(float u, float v);
 		bool addTriangle(int a, int b, int c, int uv_a = -1, int uv_b = -1, int uv_c = -1);
 		bool smoothMesh(const std::string &name, float angle);
+		bool addInstance(const std::string &base_object_name, const float m[16]);   // row-major obj_to_world
+		// the built scene's primitives [first, first + count) as the device holds them (yafaray_amd_getPrimitives)
+		bool getPrimitives(int first, int count, float *verts9, float *ng3, float *vnormals9, int *material);
 		bool createMaterial(const std::string &name, const ParamMap &p, const std::list<ParamMap> &nodes);
 		HostImage *createImage(const std::string &name, const ParamMap &p);
 		bool createTexture(const std::string &name, const ParamMap &p);
@@ -268,6 +281,9 @@ class Scene
 	private:
 		bool renderDeviceGroup(RenderParams &rp);
 		bool meshLightFaces(const std::string &name, DevLight &L, HostScene &hs);
+		bool gatherInstanced(HostScene &hs);
+		void materialRows(HostScene &hs);
+		bool lightsAndUpload(HostScene &hs);
 		std::unique_ptr<GpuRenderer> gpu_;
 		std::vector<std::unique_ptr<GpuRenderer>> extra_;   // device group members 1..
 		std::vector<int> member_devs_;                      // devices of the current members

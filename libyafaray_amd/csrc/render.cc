@@ -88,6 +88,9 @@ hipError_t yafamd_launch_fg(const DevScene *S, const DevNeeQueue *G, const DevCo
 size_t yafamd_gather_lanes(const DevScene *S);
 hipError_t yafamd_build_bvh_gpu(const float *verts_dev, const int *tris_dev, int n, void **nodes_out, void **tris_out,
                                 int *n_nodes, int *depth, int *stack_need, int *ploc_iters, YafBvh8 *w8, hipStream_t st);
+hipError_t yafamd_instance_expand(const DevInstSeg *segs, int n_segs, const float *src_verts, const int *src_tris, const float4 *src_ng,
+                                  const float4 *src_attr, int n_out_verts, int n_out_prims, float *out_verts, int *out_tris, float4 *out_ng,
+                                  float4 *out_attr, float *bounds, hipStream_t st);
 hipError_t yafamd_build_pkd(const float4 *pos_dev, uint32_t n, uint4 *nodes_dev, int *depth_out, hipStream_t st, void **scratch);
 hipError_t yafamd_build_pkd_kd(const float4 *pos_dev, const float4 *dir_dev, const float *colb_dev, uint32_t n, uint4 *nodes_dev, float4 *kpos,
                                float4 *kdir, float *kcolb, int *depth_out, hipStream_t st, void **scratch);
@@ -275,6 +278,7 @@ struct GpuRenderer::Impl
 	hipStream_t side = nullptr;
 	hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 	Buf nodes, tris, prim_ng, mats, lights, faure, faure_dim, faure_inv;
+	Buf world_verts, world_tris;   // an instanced scene's expanded vertices / indices (instexpand.hip), kept for readPrimitives
 	Buf nodes8, tris8;          // quantised BVH8 of the device-built tree and its triangles (k_trace's refill loop), or empty
 	int n_nodes8 = 0, need8 = 0, lds_top8 = 0, depth8 = 0;
 	int trace_grid_bvh4 = 0;   // the grid of the BVH4 k_trace when a BVH8 exists (transparent shadows)
@@ -560,25 +564,119 @@ static bool ensure(Logger &log_, Buf &b, size_t bytes)
 	return true;
 }
 
+bool GpuRenderer::expandInstances(const HostScene &hs, std::vector<float> *verts, std::vector<int> *tris)
+{
+	if(!ready()) return false;
+	DeviceGuard guard(device_);
+	Impl &d = *d_;
+	Buf segs, sv, st, sng, sattr, bounds;
+	if(!allocCopy(log_, segs, hs.segs.data(), hs.segs.size()) || !allocCopy(log_, sv, hs.verts.data(), hs.verts.size()) ||
+	   !allocCopy(log_, st, hs.tris.data(), hs.tris.size()) || !allocCopy(log_, sng, hs.prim_ng.data(), hs.prim_ng.size()))
+		return false;
+	if(hs.has_attr && !allocCopy(log_, sattr, hs.prim_attr.data(), hs.prim_attr.size())) return false;
+	const size_t nv = (size_t)hs.n_verts, np = (size_t)hs.n_prims;
+	bool ok = ensure(log_, bounds, 6 * sizeof(float)) && ensure(log_, d.world_verts, nv * 3 * sizeof(float)) &&
+	          ensure(log_, d.world_tris, np * 3 * sizeof(int)) && ensure(log_, d.prim_ng, np * sizeof(float4));
+	if(ok && hs.has_attr) ok = ensure(log_, d.prim_attr, np * kAttrF4 * sizeof(float4));
+	hipError_t e = hipSuccess;
+	if(ok)
+		e = yafamd_instance_expand((const DevInstSeg *)segs.p, (int)hs.segs.size(), (const float *)sv.p, (const int *)st.p, (const float4 *)sng.p,
+		                           hs.has_attr ? (const float4 *)sattr.p : nullptr, hs.n_verts, hs.n_prims, (float *)d.world_verts.p, (int *)d.world_tris.p,
+		                           (float4 *)d.prim_ng.p, hs.has_attr ? (float4 *)d.prim_attr.p : nullptr, (float *)bounds.p, d.stream);
+	float b6[6] = {};
+	if(ok && e == hipSuccess) e = hipMemcpy(b6, bounds.p, sizeof(b6), hipMemcpyDeviceToHost);
+	if(ok && e == hipSuccess && verts)
+	{
+		verts->resize(nv * 3);
+		if(nv) e = hipMemcpy(verts->data(), d.world_verts.p, nv * 3 * sizeof(float), hipMemcpyDeviceToHost);
+	}
+	if(ok && e == hipSuccess && tris)
+	{
+		tris->resize(np * 3);
+		if(np) e = hipMemcpy(tris->data(), d.world_tris.p, np * 3 * sizeof(int), hipMemcpyDeviceToHost);
+	}
+	for(Buf *b : {&segs, &sv, &st, &sng, &sattr, &bounds}) b->release();
+	if(!ok) return false;
+	HIPCHECK(e);
+	for(int a = 0; a < 3; ++a) { d.scene_lo[a] = b6[a]; d.scene_hi[a] = b6[3 + a]; }
+	return true;
+}
+
+bool GpuRenderer::hasWorldVerts() const { return d_->world_verts.p != nullptr; }
+int GpuRenderer::primitiveCount() const { return d_->n_tris; }
+
+bool GpuRenderer::readPrimitives(int first, int count, float *verts9, float *ng3, float *vnormals9, int *material)
+{
+	if(!ready()) return false;
+	DeviceGuard guard(device_);
+	Impl &d = *d_;
+	if(first < 0 || count < 0 || (int64_t)first + count > d.n_tris) { log_.error("GPU: readPrimitives: range outside of the scene's primitives"); return false; }
+	if(count == 0) return true;
+	const size_t n = (size_t)count;
+	std::vector<float> ng(4 * n), attr;
+	HIPCHECK(hipMemcpy(ng.data(), (const float4 *)d.prim_ng.p + first, n * sizeof(float4), hipMemcpyDeviceToHost));
+	if(d.has_attr && vnormals9)
+	{
+		attr.resize(n * kAttrF4 * 4);
+		HIPCHECK(hipMemcpy(attr.data(), (const float4 *)d.prim_attr.p + (size_t)first * kAttrF4, n * kAttrF4 * sizeof(float4), hipMemcpyDeviceToHost));
+	}
+	for(size_t i = 0; i < n; ++i)
+	{
+		const float *g = &ng[4 * i];
+		if(ng3) std::memcpy(ng3 + 3 * i, g, 12);
+		if(material) std::memcpy(material + i, g + 3, 4);
+		if(!vnormals9) continue;
+		uint32_t fl = 0;
+		if(!attr.empty()) std::memcpy(&fl, &attr[i * kAttrF4 * 4 + 3], 4);
+		for(int r = 0; r < 3; ++r)
+			std::memcpy(vnormals9 + 9 * i + 3 * r, (fl & ATTR_SMOOTH) ? &attr[(i * kAttrF4 + 8 + (size_t)r) * 4] : g, 12);
+	}
+	if(verts9)
+	{
+		if(!d.world_verts.p) { log_.error("GPU: readPrimitives: the scene's vertices are not on the device"); return false; }
+		std::vector<int> idx(3 * n);
+		HIPCHECK(hipMemcpy(idx.data(), (const int *)d.world_tris.p + 3 * (size_t)first, 3 * n * sizeof(int), hipMemcpyDeviceToHost));
+		int lo = idx[0], hi = idx[0];
+		for(int v : idx) { lo = std::min(lo, v); hi = std::max(hi, v); }
+		std::vector<float> vs(3 * (size_t)(hi - lo + 1));
+		HIPCHECK(hipMemcpy(vs.data(), (const float *)d.world_verts.p + 3 * (size_t)lo, vs.size() * sizeof(float), hipMemcpyDeviceToHost));
+		for(size_t k = 0; k < 3 * n; ++k) std::memcpy(verts9 + 3 * k, &vs[3 * (size_t)(idx[k] - lo)], 12);
+	}
+	return true;
+}
+
 bool GpuRenderer::upload(HostScene &hs)
 {
 	if(!ready()) return false;
 	DeviceGuard guard(device_);
 	Impl &d = *d_;
+	// object instances: this device expands them into world_verts / world_tris / prim_ng / prim_attr
+	if(hs.instanced) { if(!expandInstances(hs)) return false; }
+	else for(Buf *b : {&d.world_verts, &d.world_tris}) b->release();
 	if(hs.gpu_build)
 	{
 		// device build: PLOC + BVH4 collapse (bvhgpu.hip); only the mesh crosses PCIe
-		// (the scene bounds: ray binning quantises ray origins in them)
-		for(int a = 0; a < 3; ++a) { d.scene_lo[a] = 3.4e38f; d.scene_hi[a] = -3.4e38f; }
-		for(size_t k = 0; k + 2 < hs.verts.size(); k += 3)
-			for(int a = 0; a < 3; ++a)
-			{
-				d.scene_lo[a] = std::min(d.scene_lo[a], hs.verts[k + (size_t)a]);
-				d.scene_hi[a] = std::max(d.scene_hi[a], hs.verts[k + (size_t)a]);
-			}
+		// (the scene bounds: ray binning quantises ray origins in them; expandInstances reduced them
+		// on the device for an instanced scene)
 		Buf v, t;
-		if(!allocCopy(log_, v, hs.verts.data(), hs.verts.size())) return false;
-		if(!allocCopy(log_, t, hs.tris.data(), hs.tris.size())) return false;
+		if(hs.instanced)
+		{
+			// borrowed for the build: the expanded arrays stay in world_verts / world_tris
+			v.p = d.world_verts.p;
+			t.p = d.world_tris.p;
+		}
+		else
+		{
+			for(int a = 0; a < 3; ++a) { d.scene_lo[a] = 3.4e38f; d.scene_hi[a] = -3.4e38f; }
+			for(size_t k = 0; k + 2 < hs.verts.size(); k += 3)
+				for(int a = 0; a < 3; ++a)
+				{
+					d.scene_lo[a] = std::min(d.scene_lo[a], hs.verts[k + (size_t)a]);
+					d.scene_hi[a] = std::max(d.scene_hi[a], hs.verts[k + (size_t)a]);
+				}
+			if(!allocCopy(log_, v, hs.verts.data(), hs.verts.size())) return false;
+			if(!allocCopy(log_, t, hs.tris.data(), hs.tris.size())) return false;
+		}
 		d.nodes.release();
 		d.tris.release();
 		d.nodes8.release();
@@ -592,6 +690,7 @@ bool GpuRenderer::upload(HostScene &hs)
 		YafBvh8 w8;
 		const hipError_t e = yafamd_build_bvh_gpu((const float *)v.p, (const int *)t.p, hs.n_prims, &np, &tp, &nn, &depth, &need, &iters,
 		                                          (b8 && *b8 == '0') ? nullptr : &w8, d.stream);
+		if(hs.instanced) v.p = t.p = nullptr;
 		v.release();
 		t.release();
 		if(w8.nodes)
@@ -624,7 +723,7 @@ bool GpuRenderer::upload(HostScene &hs)
 		if(!allocCopy(log_, d.nodes, hs.bvh.nodes.data(), hs.bvh.nodes.size())) return false;
 		if(!allocCopy(log_, d.tris, hs.bvh.tris.data(), hs.bvh.tris.size())) return false;
 	}
-	if(!allocCopy(log_, d.prim_ng, hs.prim_ng.data(), hs.prim_ng.size())) return false;
+	if(!hs.instanced && !allocCopy(log_, d.prim_ng, hs.prim_ng.data(), hs.prim_ng.size())) return false;
 	if(!allocCopy(log_, d.mats, hs.mats.data(), hs.mats.size())) return false;
 	if(!allocCopy(log_, d.lights, hs.lights.data(), hs.lights.size())) return false;
 	d.host_lights = hs.lights;
@@ -639,7 +738,7 @@ bool GpuRenderer::upload(HostScene &hs)
 	d.n_textures = (int)hs.textures.size();
 	if(hs.has_attr)
 	{
-		if(!allocCopy(log_, d.prim_attr, hs.prim_attr.data(), hs.prim_attr.size())) return false;
+		if(!hs.instanced && !allocCopy(log_, d.prim_attr, hs.prim_attr.data(), hs.prim_attr.size())) return false;
 		if(!allocCopy(log_, d.shader_nodes, hs.shader_nodes.data(), hs.shader_nodes.size())) return false;
 		if(!allocCopy(log_, d.textures, hs.textures.data(), hs.textures.size())) return false;
 		if(!allocCopy(log_, d.texels, hs.texels.data(), hs.texels.size())) return false;

@@ -27,8 +27,8 @@ struct HostScene
 {
 	BvhOutput bvh;                       // host build (nodes + triangle records), or metadata of the GPU build
 	bool gpu_build = false;              // build the BVH4 on the device from verts / tris (bvhgpu.hip)
-	std::vector<float> verts;            // xyz per vertex   (gpu_build only)
-	std::vector<int> tris;               // 3 indices per triangle (gpu_build only)
+	std::vector<float> verts;            // xyz per vertex   (gpu_build or instanced only)
+	std::vector<int> tris;               // 3 indices per triangle (gpu_build or instanced only)
 	int ploc_iters = 0;                  // PLOC iterations of the GPU build
 	std::vector<float> prim_ng;          // 4 floats per primitive
 	std::vector<DevMaterial> mats;
@@ -39,6 +39,13 @@ struct HostScene
 	std::vector<float> mesh_nodes;       // each meshlight's BVH2 over its faces (16 floats per node)
 	std::vector<float> mesh_btris;       // ... and its triangle records in leaf order (12 floats each)
 	int n_prims = 0;
+	// A scene with object instances (Scene::addInstance): verts / tris / prim_ng / prim_attr hold the
+	// SOURCE rows — every visible plain mesh and every instanced base once, in object space, tris local
+	// to their object — and `segs` says how the device expands them (instexpand.hip) into the n_verts
+	// vertices and n_prims primitives of the world-space arrays.  The host never holds the expanded scene.
+	bool instanced = false;
+	std::vector<DevInstSeg> segs;
+	int n_verts = 0;                     // output vertices (instanced only)
 	// surface attributes / textures / shader nodes (texeval.h), only when has_attr
 	bool has_attr = false;
 	std::vector<float> prim_attr;        // kAttrF4 float4 per primitive
@@ -185,6 +192,16 @@ class GpuRenderer
 		static int currentDevice();
 		static void enablePeerAccess(const std::vector<int> &devices);
 		bool upload(HostScene &hs);   // fills hs.bvh's metadata when the BVH is built on the device
+		// An instanced scene's world-space arrays, expanded on this device (instexpand.hip) and kept there;
+		// verts / tris (optional): copied back for the host's SAH builder
+		bool expandInstances(const HostScene &hs, std::vector<float> *verts = nullptr, std::vector<int> *tris = nullptr);
+		// Read-back of the uploaded scene's primitives [first, first + count): geometric normal (3), vertex
+		// normals (9: the geometric normal where the primitive is not smooth), material index, and the
+		// world-space vertices (9) — these only where hasWorldVerts(): the device keeps a vertex array for
+		// instanced scenes only (a plain scene's vertices are the host objects' own); null = skipped
+		bool readPrimitives(int first, int count, float *verts9, float *ng3, float *vnormals9, int *material);
+		bool hasWorldVerts() const;
+		int primitiveCount() const;
 		bool render(RenderParams &rp, volatile bool *canceled);
 		int lastPassCount() const { return passes_done_; }
 		uint32_t samplingOffset() const { return sampling_offset_; }   // ImageFilm::sampling_offset_ after the last pass

@@ -727,7 +727,7 @@ YD SurfAttr surfAttr(const float4 *attr, const float4 *prim_ng, int prim, V3 o, 
 	else
 	{
 		s.orco_p = p;
-		s.orco_ng = s.ng;
+		s.orco_ng = (fl & ATTR_BASE_NG) ? xyz4(a[3]) : s.ng;
 	}
 	if(fl & ATTR_UV)
 	{

@@ -203,6 +203,8 @@ class Object:
     nuv: int = 0
     smooth_angle: Optional[float] = None   # yafaray_smoothMesh(name, angle) after endObject
     has_orco: bool = True                  # with SceneSpec.orco: addVertexWithOrco (else addVertex)
+    is_base: bool = False                  # "is_base_object": shows only through its instances
+    visibility: str = "normal"             # or "invisible" (hides the object and its instances)
 
 
 @dataclass
@@ -223,6 +225,8 @@ class SceneSpec:
     tri_uv: Optional[np.ndarray] = None     # (M, 3) global uv indices (-1: addTriangle)
     images: List[ImageSpec] = field(default_factory=list)
     textures: List[TextureSpec] = field(default_factory=list)
+    # object instances: (base object name, (3, 4) or (4, 4) float32 obj_to_world), added after the objects
+    instances: list = field(default_factory=list)
 
     def render_lights(self):
         """Lights in the order the integrators see them: by name (render_view.cc:61, std::map)."""
@@ -572,6 +576,10 @@ def apply(spec: SceneSpec, api) -> None:
         use_orco = spec.orco is not None and o.has_orco
         api.paramsSetBool("has_orco", use_orco)
         api.paramsSetBool("has_uv", o.nuv > 0)
+        if o.is_base:
+            api.paramsSetBool("is_base_object", True)
+        if o.visibility != "normal":
+            api.paramsSetString("visibility", o.visibility)
         api.createObject(o.name)
         if use_orco:
             for v, oc in zip(spec.verts[o.v0:o.v0 + o.nv], spec.orco[o.v0:o.v0 + o.nv]):
@@ -613,6 +621,9 @@ def apply(spec: SceneSpec, api) -> None:
         api.endObject()
         if o.smooth_angle is not None:
             api.smoothMesh(o.name, float(o.smooth_angle))
+    for base, m in spec.instances:
+        if not api.addInstance(base, m):
+            raise RuntimeError("addInstance('%s') failed: %s" % (base, api.last_error()))
     cam = spec.camera
     api.paramsClearAll()
     api.paramsSetString("type", "perspective")
@@ -807,3 +818,135 @@ def cornell_transparent_shadows(width=64, height=48, spp=2, integrator="directli
     r = dataclasses.replace(s.render, transp_shad=True, shadow_depth=shadow_depth, raydepth=2)
     return dataclasses.replace(s, verts=verts, tris=tris, tri_mat=tri_mat, materials=mats, lights=lights,
                                objects=b.objects, render=r)
+
+
+# ---------------------------------------------------------------------------------------------
+# object instances (yafaray_addInstance): the per-primitive rules in numpy float32, one rounding per
+# operation, in the expression order of the reference's matrix4.h:78-90 and vector.h:201-209
+# ---------------------------------------------------------------------------------------------
+
+def _m34(m):
+    m = np.asarray(m, np.float32)
+    return np.ascontiguousarray(m[:3, :4])
+
+
+def xform_points(m, p):
+    """M * Point3: m[i][0] x + m[i][1] y + m[i][2] z + m[i][3] (row 3 is never read)."""
+    m, p = _m34(m), np.asarray(p, np.float32).reshape(-1, 3)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return np.stack([m[i, 0] * x + m[i, 1] * y + m[i, 2] * z + m[i, 3] for i in range(3)], -1)
+
+
+def xform_vectors(m, v):
+    """M * Vec3: no translation, no inverse transpose."""
+    m, v = _m34(m), np.asarray(v, np.float32).reshape(-1, 3)
+    x, y, z = v[:, 0], v[:, 1], v[:, 2]
+    return np.stack([m[i, 0] * x + m[i, 1] * y + m[i, 2] * z for i in range(3)], -1)
+
+
+def normalize_f32(v):
+    """Vec3::normalize: len = x x + y y + z z; if len != 0: v *= 1 / sqrt(len)."""
+    v = np.asarray(v, np.float32).reshape(-1, 3)
+    l = v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1] + v[:, 2] * v[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        inv = np.float32(1.0) / np.sqrt(l)
+        scaled = v * inv[:, None]
+    return np.where((l != 0)[:, None], scaled, v).astype(np.float32)
+
+
+def face_normals(verts, tris):
+    """normalize((b - a) ^ (c - a)) per triangle (primitive_face.cc:130-134)."""
+    verts = np.asarray(verts, np.float32)
+    a, b, c = verts[tris[:, 0]], verts[tris[:, 1]], verts[tris[:, 2]]
+    e1, e2 = b - a, c - a
+    cr = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                   e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], -1)
+    return normalize_f32(cr)
+
+
+def instance_normal_rules_agree(verts, tris, m):
+    """Per face of a base mesh (object-space verts, local tris): whether the instance's geometric normal
+    normalize(M * ng_base) equals, by value, the normal recomputed from the transformed vertices.  Only
+    where this holds for every face is a flattened mesh the reference's instance."""
+    rule = normalize_f32(xform_vectors(m, face_normals(verts, tris)))
+    recomputed = face_normals(xform_points(m, verts), tris)
+    return np.all(rule == recomputed, axis=1)
+
+
+def flatten_instances(spec: SceneSpec) -> SceneSpec:
+    """`spec` with every instance written out as a plain mesh object and no instances left: the visible
+    non-base objects in their order, then one object per instance in the order of spec.instances (the
+    order apply() issues them in).  Positions are M * vertex; exported per-vertex normals become
+    normalize(M * n); orco coordinates, uv values and materials are carried over.  The flattened
+    primitive's geometric normal is recomputed from its vertices, so the result is the instanced scene
+    only where instance_normal_rules_agree holds; and without orco its orco normal is the world one."""
+    import dataclasses
+    by_name = {o.name: o for o in spec.objects}
+    V, T, TM, OR, NR, UV, TUV, objs = [], [], [], [], [], [], [], []
+    nv = nt = nuv = 0
+
+    def emit(o, name, m):
+        nonlocal nv, nt, nuv
+        v = np.asarray(spec.verts[o.v0:o.v0 + o.nv], np.float32)
+        V.append(v if m is None else xform_points(m, v))
+        T.append(np.asarray(spec.tris[o.t0:o.t0 + o.nt], np.int32) - o.v0 + nv)
+        TM.append(np.asarray(spec.tri_mat[o.t0:o.t0 + o.nt], np.int32))
+        if spec.orco is not None:
+            OR.append(np.asarray(spec.orco[o.v0:o.v0 + o.nv], np.float32))
+        if spec.normals is not None:
+            n = np.asarray(spec.normals[o.v0:o.v0 + o.nv], np.float32)
+            NR.append(n if m is None else normalize_f32(xform_vectors(m, n)))
+        if spec.uvs is not None and o.nuv:
+            UV.append(np.asarray(spec.uvs[o.uv0:o.uv0 + o.nuv], np.float32))
+        if spec.tri_uv is not None:
+            tu = np.asarray(spec.tri_uv[o.t0:o.t0 + o.nt], np.int32)
+            TUV.append(np.where(tu >= 0, tu - o.uv0 + nuv, -1).astype(np.int32))
+        objs.append(dataclasses.replace(o, name=name, v0=nv, t0=nt, uv0=nuv, is_base=False))
+        nv, nt, nuv = nv + o.nv, nt + o.nt, nuv + o.nuv
+
+    for o in spec.objects:
+        if not o.is_base and o.visibility != "invisible":
+            emit(o, o.name, None)
+    for k, (base, m) in enumerate(spec.instances):
+        o = by_name[base]
+        if o.smooth_angle is not None:
+            raise NotImplementedError("flatten_instances: the normals of a smoothMesh base are made by the library")
+        if o.visibility != "invisible":
+            emit(o, "%s-%d" % (base, len(spec.objects) + k + 1), m)
+
+    def cat(parts, shape, dt):
+        return np.concatenate(parts).astype(dt) if parts else np.zeros(shape, dt)
+    return dataclasses.replace(
+        spec, verts=cat(V, (0, 3), np.float32), tris=cat(T, (0, 3), np.int32), tri_mat=cat(TM, (0,), np.int32),
+        objects=objs, instances=[], orco=None if spec.orco is None else cat(OR, (0, 3), np.float32),
+        normals=None if spec.normals is None else cat(NR, (0, 3), np.float32),
+        uvs=None if spec.uvs is None else cat(UV, (0, 2), np.float32),
+        tri_uv=None if spec.tri_uv is None else cat(TUV, (0, 3), np.int32))
+
+
+# obj_to_world of cornell_instanced's three boxes: power-of-two scales (the second non-uniform), 90 degree
+# axis rotations and dyadic translations, so that every product and sum of the vertex and normal rules is
+# exact and both normal rules agree on all 36 faces (instance_normal_rules_agree)
+CORNELL_INSTANCE_MATRICES = (
+    ((0.5, 0.0, 0.0, 0.375), (0.0, 0.5, 0.0, -0.25), (0.0, 0.0, 0.5, 0.25)),
+    ((0.0, -0.5, 0.0, -0.375), (0.5, 0.0, 0.0, 0.375), (0.0, 0.0, 1.0, 0.5)),
+    ((0.0, 0.0, 0.25, 0.125), (0.25, 0.0, 0.0, -0.5), (0.0, 0.25, 0.0, 1.5)),
+)
+
+
+def cornell_instanced(width=80, height=60, spp=4, bounces=8, rr=False, integrator="pathtracing", **kw) -> SceneSpec:
+    """The Cornell room whose boxes are instances of one is_base cube [-0.5, 0.5]^3 (a short box, a tall
+    box rotated by 90 degrees, a small box hanging in the air)."""
+    import dataclasses
+    s = cornell(width, height, spp=spp, bounces=bounces, rr=rr, integrator=integrator, **kw)
+    room = [o for o in s.objects if o.name not in ("short_box", "tall_box")]
+    nv, nt = sum(o.nv for o in room), sum(o.nt for o in room)
+    assert [o.v0 for o in room] == list(np.cumsum([0] + [o.nv for o in room[:-1]]))   # the room comes first
+    corners = [(x, y, z) for z in (-0.5, 0.5) for (x, y) in ((-0.5, -0.5), (0.5, -0.5), (0.5, 0.5), (-0.5, 0.5))]
+    _, ctris = _box(0.0, 0.0, 0.5, 0.5, 1.0, 0.0)
+    verts = np.concatenate([s.verts[:nv], np.asarray(corners, np.float32)])
+    tris = np.concatenate([s.tris[:nt], np.asarray(ctris, np.int32) + nv])
+    tri_mat = np.concatenate([s.tri_mat[:nt], np.zeros(len(ctris), np.int32)])
+    objs = room + [Object("cube", nv, 8, nt, len(ctris), is_base=True)]
+    inst = [("cube", np.asarray(m, np.float32)) for m in CORNELL_INSTANCE_MATRICES]
+    return dataclasses.replace(s, verts=verts, tris=tris, tri_mat=tri_mat, objects=objs, instances=inst)
