@@ -103,6 +103,19 @@ YAFARAY_C_API_EXPORT int yafaray_amd_getPrimitives(yafaray_Interface_t *interfac
 
 /* Film of the last render: rgba width*height*4 floats (normalised, = put-pixel values), weights width*height. */
 YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_getFilm(const yafaray_Interface_t *interface, float *rgba, float *weights);
+/* Render layers (LIBYAFARAY_AMD_1.8).  yafaray_defineLayer accepts, beside "combined", the first-hit layers
+ * z-depth-abs, z-depth-norm, mist, debug-normal-geom, debug-normal-smooth, debug-uv, debug-barycentric-uvw,
+ * adv-diffuse-color, obj-index-abs, obj-index-norm, mat-index-abs and mat-index-norm; every other type
+ * warns and is not produced.
+ * getLayerCount: the layers the next render produces, "combined" included (0 without a scene).
+ * getLayerName: layer k's type name in the reference's layer order ("combined" first); NULL out of range.
+ *   The string lives until the scene's layers change. */
+YAFARAY_C_API_EXPORT int yafaray_amd_getLayerCount(const yafaray_Interface_t *interface);
+YAFARAY_C_API_EXPORT const char *yafaray_amd_getLayerName(const yafaray_Interface_t *interface, int k);
+/* One layer of the last render's film: rgba width*height*4 floats, the values put-pixel reports for the
+ * layer — normalised, ceil() of the absolute index layers, alpha 1 for an image type without alpha.
+ * Also serves layers defined without exported_image_type (no callbacks).  False: no such layer rendered. */
+YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_getFilmLayer(const yafaray_Interface_t *interface, const char *layer, float *rgba);
 /* Film straight into device memory (rows [y0, y1) of a width*height*4 float buffer on the render device). */
 YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_getFilmDevice(const yafaray_Interface_t *interface, void *rgba_dev, int y0, int y1);
 

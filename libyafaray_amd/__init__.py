@@ -140,6 +140,10 @@ def lib():
             "yafaray_amd_traceShadow": (b, [vp, C.POINTER(C.c_float), i, C.POINTER(C.c_int)]),
             "yafaray_amd_getFilm": (b, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
             "yafaray_amd_getFilmDevice": (b, [vp, vp, i, i]),
+            "yafaray_amd_getLayerCount": (i, [vp]),
+            "yafaray_amd_getLayerName": (cp, [vp, i]),
+            "yafaray_amd_getFilmLayer": (b, [vp, cp, C.POINTER(C.c_float)]),
+            "yafaray_getLayersTable": (vp, [vp]),
             "yafaray_amd_setTileRowShard": (None, [vp, i, i]),
             "yafaray_amd_setRowBandShard": (None, [vp, i, i]),
             "yafaray_amd_setRowBandRange": (None, [vp, i, i, i]),
@@ -169,7 +173,9 @@ def lib():
                                                C.POINTER(C.c_uint64), i]),
         }
         # LIBYAFARAY_AMD_1.4 / 1.7 (variant builds of older sources lack them)
-        optional = {"yafaray_amd_buildInfo", "yafaray_amd_getGroupReport", "yafaray_amd_getPrimitives"}
+        # ... / 1.8: the render layers
+        optional = {"yafaray_amd_buildInfo", "yafaray_amd_getGroupReport", "yafaray_amd_getPrimitives",
+                    "yafaray_amd_getLayerCount", "yafaray_amd_getLayerName", "yafaray_amd_getFilmLayer"}
         for name, (res, args) in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -292,7 +298,10 @@ class Interface:
         return e.decode() if e else ""
 
     # --- render ---
-    def render(self, progress=None, put_pixel=None, flush_area=None, flush=None, highlight_area=None):
+    def render(self, progress=None, put_pixel=None, flush_area=None, flush=None, highlight_area=None, put_layer_pixel=None,
+               notify_layer=None):
+        """put_pixel(x, y, r, g, b, a) sees the combined layer; put_layer_pixel(layer, x, y, r, g, b, a) every exported
+        layer with the layer name the library reports; notify_layer(layer, exported_name, width, height, channels)."""
         # every callback is (re)registered, a missing one as NULL (an empty CFUNCTYPE instance): the library
         # keeps the pointers between renders, and the previous render's ctypes thunks are released below
         # (self._keep) — a render without a callback after one with it called a freed thunk
@@ -300,11 +309,20 @@ class Interface:
         cb = FlushAreaCb(lambda v, aid, x0, y0, x1, y1, d: highlight_area(aid, x0, y0, x1, y1)) if highlight_area is not None else FlushAreaCb()
         self.L.yafaray_setRenderHighlightAreaCallback(self.h, cb, None)
         cbs.append(cb)
-        cb = PutPixelCb(lambda v, l, x, y, r, g, b, a, d: put_pixel(x, y, r, g, b, a)) if put_pixel is not None else PutPixelCb()
+        def _put(v, l, x, y, r, g, b, a, d):
+            if put_layer_pixel is not None:
+                put_layer_pixel(l.decode(), x, y, r, g, b, a)
+            if put_pixel is not None and l == b"combined":
+                put_pixel(x, y, r, g, b, a)
+        cb = PutPixelCb(_put) if (put_pixel is not None or put_layer_pixel is not None) else PutPixelCb()
         self.L.yafaray_setRenderPutPixelCallback(self.h, cb, None)
         cbs.append(cb)
         cb = FlushAreaCb(lambda v, aid, x0, y0, x1, y1, d: flush_area(aid, x0, y0, x1, y1)) if flush_area is not None else FlushAreaCb()
         self.L.yafaray_setRenderFlushAreaCallback(self.h, cb, None)
+        cbs.append(cb)
+        cb = (NotifyLayerCb(lambda l, e, w, h, c, d: notify_layer(l.decode(), (e or b"").decode(), w, h, c)) if notify_layer is not None
+              else NotifyLayerCb())
+        self.L.yafaray_setRenderNotifyLayerCallback(self.h, cb, None)
         cbs.append(cb)
         cb = FlushCb(lambda v, d: flush()) if flush is not None else FlushCb()
         self.L.yafaray_setRenderFlushCallback(self.h, cb, None)
@@ -330,6 +348,26 @@ class Interface:
                                           wt.ctypes.data_as(C.POINTER(C.c_float))):
             raise RuntimeError("no film: " + self.last_error())
         return rgba, wt
+
+    def layers(self):
+        """The type names of the layers the next render produces, "combined" first (yafaray_amd_getLayerName)."""
+        n = int(self.L.yafaray_amd_getLayerCount(self.h))
+        return [self.L.yafaray_amd_getLayerName(self.h, k).decode() for k in range(n)]
+
+    def film_layer(self, name):
+        """One layer of the last render's film, (h, w, 4) float32, as put-pixel reports it (yafaray_amd_getFilmLayer)."""
+        w, h = self.L.yafaray_getSceneFilmWidth(self.h), self.L.yafaray_getSceneFilmHeight(self.h)
+        rgba = np.empty((h, w, 4), np.float32)
+        if not self.L.yafaray_amd_getFilmLayer(self.h, _b(name), rgba.ctypes.data_as(C.POINTER(C.c_float))):
+            raise RuntimeError(f"no film layer '{name}': " + self.last_error())
+        return rgba
+
+    def layers_table(self) -> str:
+        """yafaray_getLayersTable: one line per exported layer."""
+        p = self.L.yafaray_getLayersTable(self.h)
+        s = C.cast(p, C.c_char_p).value.decode()
+        self.L.yafaray_deallocateCharPointer(p)
+        return s
 
     def stats(self) -> dict:
         s = Stats()

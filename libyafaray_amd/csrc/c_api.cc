@@ -348,10 +348,7 @@ void yafaray_defineLayer(yafaray_Interface_t *interface)
 	Interface *it = I(interface);
 	Scene *s = it->sc();
 	if(!s) return;
-	std::string type;
-	it->params.get("type", type);
-	if(type != "combined") it->logger.warning("Layers: layer '" + type + "' is not produced by the GPU core (combined only)");
-	s->layers.push_back(type);
+	s->defineLayer(it->params);
 }
 
 // ---- logging ----
@@ -434,8 +431,8 @@ char *yafaray_getVersionString() { return dupString("4.0.0-mi355x (libYafaRay C 
 
 char *yafaray_getLayersTable(const yafaray_Interface_t *interface)
 {
-	(void)interface;
-	return dupString("combined\tCombined\tColorAlpha\n");
+	const Interface *it = I(interface);
+	return dupString(it->scene ? it->scene->layersTable() : std::string("combined\tCombined\tColorAlpha\n"));
 }
 
 char *yafaray_getViewsTable(const yafaray_Interface_t *interface)
@@ -524,6 +521,29 @@ yafaray_bool_t yafaray_amd_getFilm(const yafaray_Interface_t *interface, float *
 	if(rgba) std::memcpy(rgba, it->scene->film_rgba.data(), it->scene->film_rgba.size() * 4);
 	if(weights) std::memcpy(weights, it->scene->film_weights.data(), it->scene->film_weights.size() * 4);
 	return YAFARAY_BOOL_TRUE;
+}
+
+int yafaray_amd_getLayerCount(const yafaray_Interface_t *interface)
+{
+	const Interface *it = I(interface);
+	return it->scene ? 1 + (int)it->scene->extraLayers().size() : 0;
+}
+
+const char *yafaray_amd_getLayerName(const yafaray_Interface_t *interface, int k)
+{
+	const Interface *it = I(interface);
+	if(!it->scene || k < 0) return nullptr;
+	if(k == 0) return "combined";
+	const std::vector<const LayerDesc *> ls = it->scene->extraLayers();
+	return (size_t)k <= ls.size() ? ls[(size_t)k - 1]->name.c_str() : nullptr;
+}
+
+yafaray_bool_t yafaray_amd_getFilmLayer(const yafaray_Interface_t *interface, const char *layer, float *rgba)
+{
+	const Interface *it = I(interface);
+	if(!it->scene || !layer || !rgba) return YAFARAY_BOOL_FALSE;
+	if(std::string(layer) == "combined") return yafaray_amd_getFilm(interface, rgba, nullptr);
+	return it->scene->getFilmLayer(layer, rgba) ? YAFARAY_BOOL_TRUE : YAFARAY_BOOL_FALSE;
 }
 
 yafaray_bool_t yafaray_amd_getFilmDevice(const yafaray_Interface_t *interface, void *rgba_dev, int y0, int y1)

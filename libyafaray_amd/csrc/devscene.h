@@ -383,6 +383,35 @@ struct DevFilm
 	int crop_x0, crop_y0;          // cropped film: the sample positions hash the camera pixel (x + crop_x0, y + crop_y0)
 };
 
+// ---- render layers (layers_kernels.h): the first-hit layers of a render that defines any ----
+// The kinds in the reference's LayerDef::Type order (the order of the film's layer planes, of the
+// callbacks and of the film file).
+enum : int
+{
+	LK_BARYCENTRIC = 0, LK_DIFFUSE_COLOR, LK_MAT_INDEX_ABS, LK_MAT_INDEX_NORM, LK_MIST, LK_NORMAL_GEOM, LK_NORMAL_SMOOTH,
+	LK_OBJ_INDEX_ABS, LK_OBJ_INDEX_NORM, LK_UV, LK_ZDEPTH_ABS, LK_ZDEPTH_NORM, LK_COUNT
+};
+
+// What the layer kernels read besides the scene: the defined layers (kind[0 .. n), ascending), the
+// per-primitive attribute rows (DevScene::prim_attr's layout; uploaded for the layers when the
+// scene itself has none), the index tables and the depth range.  One first-hit record per camera
+// sample, at the sample buffer's index (pixel * spp + s): (t, primitive bits, u, v) — t of a miss is
+// the camera ray's own tmax, its primitive -1; (u, v) are the Moller-Trumbore coordinates.
+struct DevLayers
+{
+	int n;
+	int kind[LK_COUNT];
+	const float4 *prim_attr;
+	const float *mat_index;        // per material: mat_pass_index
+	const int2 *obj_seg;           // (first primitive, object_index) per object, ascending first primitive
+	int n_obj_seg;
+	int n_prims, n_mats;           // records outside of them count as misses (rows a group member does not own hold none)
+	float mat_highest, obj_highest;   // Material::material_index_highest_ / ObjectBasic::highest_object_index_
+	const float *depth;            // (min_depth_, max_depth_) of TiledIntegrator::precalcDepths
+	float4 *rec;                   // first-hit records
+	float4 *albedo;                // adv-diffuse-color per sample (null: layer not defined)
+};
+
 // Per-chunk wavefront state (structure of arrays, capacity = chunk slots).
 struct DevPaths
 {

@@ -39,13 +39,14 @@ bool save(Logger &log, const std::string &file, const Film &f)
 		log.warning("imageFilm: could not open '" + file + "' for writing");
 		return false;
 	}
-	const int32_t hdr[7] = {f.width, f.height, f.cx0, f.cx1, f.cy0, f.cy1, 1};
+	const int32_t hdr[7] = {f.width, f.height, f.cx0, f.cx1, f.cy0, f.cy1, f.layerCount()};
 	const uint32_t offs[3] = {f.computer_node, f.base_sampling_offset, f.sampling_offset};
 	bool ok = fwrite(kHeader, 1, sizeof(kHeader), fp) == sizeof(kHeader);   // string + its '\0' (file.cc:190-194)
 	ok = ok && fwrite(offs, sizeof(uint32_t), 3, fp) == 3;
 	ok = ok && fwrite(hdr, sizeof(int32_t), 7, fp) == 7;
 	ok = ok && fwrite(f.weights.data(), sizeof(float), f.weights.size(), fp) == f.weights.size();
 	ok = ok && fwrite(f.rgba.data(), sizeof(float), f.rgba.size(), fp) == f.rgba.size();
+	ok = ok && fwrite(f.layers.data(), sizeof(float), f.layers.size(), fp) == f.layers.size();
 	fclose(fp);
 	if(!ok) log.warning("imageFilm: error while writing '" + file + "'");
 	return ok;
@@ -73,7 +74,7 @@ bool load(Logger &log, const std::string &file, const Film &expect, Film &out)
 	int32_t dims[7] = {0, 0, 0, 0, 0, 0, 0};
 	bool ok = fread(offs, sizeof(uint32_t), 3, fp) == 3;
 	static const char *names[6] = {"Image width", "Image height", "Border cx0", "Border cx1", "Border cy0", "Border cy1"};
-	const int want[7] = {expect.width, expect.height, expect.cx0, expect.cx1, expect.cy0, expect.cy1, 1};
+	const int want[7] = {expect.width, expect.height, expect.cx0, expect.cx1, expect.cy0, expect.cy1, expect.layerCount()};
 	for(int k = 0; ok && k < 7; ++k)
 	{
 		ok = fread(&dims[k], sizeof(int32_t), 1, fp) == 1;
@@ -95,6 +96,8 @@ bool load(Logger &log, const std::string &file, const Film &expect, Film &out)
 	// a short file leaves the rest of the film at zero, as the reference's unchecked reads do
 	ok = ok && fread(out.weights.data(), sizeof(float), n, fp) == n;
 	ok = ok && fread(out.rgba.data(), sizeof(float), 4 * n, fp) == 4 * n;
+	out.layers.assign(expect.layers.size(), 0.f);
+	ok = ok && fread(out.layers.data(), sizeof(float), out.layers.size(), fp) == out.layers.size();
 	fclose(fp);
 	if(!ok) log.warning("imageFilm: film file '" + file + "' is truncated");
 	return true;
@@ -152,6 +155,7 @@ bool loadAllInFolder(Logger &log, const std::string &path, Film &acc)
 		any = true;
 		for(size_t i = 0; i < acc.weights.size(); ++i) acc.weights[i] = acc.weights[i] + f.weights[i];
 		for(size_t i = 0; i < acc.rgba.size(); ++i) acc.rgba[i] = acc.rgba[i] + f.rgba[i];
+		for(size_t i = 0; i < acc.layers.size() && i < f.layers.size(); ++i) acc.layers[i] = acc.layers[i] + f.layers[i];
 		acc.sampling_offset = std::max(acc.sampling_offset, f.sampling_offset);
 		acc.base_sampling_offset = std::max(acc.base_sampling_offset, f.base_sampling_offset);
 	}

@@ -23,6 +23,10 @@ struct Film
 	int width = 0, height = 0, cx0 = 0, cx1 = 0, cy0 = 0, cy1 = 0;
 	std::vector<float> weights;   // [height * width]
 	std::vector<float> rgba;      // [height * width * 4], the "combined" layer
+	// the other layers with an image, in the reference's layer order: [n * height * width * 4]; the file's
+	// layer count is 1 + n, and a film whose count differs is refused
+	std::vector<float> layers;
+	int layerCount() const { return 1 + (int)(layers.size() / (4 * (size_t)(width > 0 ? width : 1) * (size_t)(height > 0 ? height : 1))); }
 };
 
 // film_load_save_mode (imagefilm.cc:89-91)

@@ -327,6 +327,13 @@ bool Scene::createObject(const std::string &name, const ParamMap &p)
 	MeshObject &o = objects[name];
 	o.name = name;
 	p.get("is_base_object", o.is_base);
+	// object_mesh.cc:39-53 + ObjectBasic::setObjectIndex (object_basic.cc:43-47)
+	{
+		int object_index = 0;
+		p.get("object_index", object_index);
+		o.object_index = (unsigned int)object_index;
+		if(highest_object_index < o.object_index) highest_object_index = o.object_index;
+	}
 	p.get("visibility", o.visibility);
 	// visibility::fromString (include/common/visibility.h:36-43): unknown strings are "normal"
 	if(o.visibility == "shadow_only" || o.visibility == "no_shadows")
@@ -681,6 +688,12 @@ bool Scene::createMaterial(const std::string &name, const ParamMap &p, const std
 		}
 		if(p.get("receive_shadows", b)) m.receive_shadows = b ? 1 : 0;
 		if(p.get("flat_material", b)) m.flat = b ? 1 : 0;
+		// material_shiny_diffuse.cc:506-546 + Material::setMaterialIndex (material.h:155-159); the other
+		// material types of the GPU core do not read it (their index stays 0)
+		int mat_pass_index = 0;
+		p.get("mat_pass_index", mat_pass_index);
+		mat_pass_index_of[name] = (unsigned int)mat_pass_index;
+		if(highest_material_index < (unsigned int)mat_pass_index) highest_material_index = (unsigned int)mat_pass_index;
 	}
 	else if(type == "light_mat")
 	{
@@ -1074,6 +1087,175 @@ bool Scene::meshLightFaces(const std::string &name, DevLight &L, HostScene &hs)
 	return true;
 }
 
+// ---- render layers (Scene::defineLayer, scene.cc:665-727; layer_definitions.cc:27-101) ----
+namespace
+{
+// (image types: texture.h's IMG_*)
+// The reference's layer types in LayerDef::Type order with their default image types; kind: the
+// LK_* the GPU core produces (-1: "combined" itself or a type it does not produce)
+struct LayerTypeDef { const char *name; int image_type; int kind; };
+const LayerTypeDef kLayerTypes[] = {
+	{"combined", IMG_COLOR_ALPHA, -1}, {"debug-aa-samples", IMG_COLOR, -1}, {"ao", IMG_COLOR, -1}, {"ao-clay", IMG_GRAY, -1},
+	{"debug-barycentric-uvw", IMG_COLOR, LK_BARYCENTRIC}, {"debug-dp-lengths", IMG_COLOR, -1}, {"debug-dpdu", IMG_COLOR, -1},
+	{"debug-dpdv", IMG_COLOR, -1}, {"debug-dpdx", IMG_COLOR, -1}, {"debug-dpdxy", IMG_COLOR, -1}, {"debug-dpdy", IMG_COLOR, -1},
+	{"debug-dsdu", IMG_COLOR, -1}, {"debug-dsdv", IMG_COLOR, -1}, {"debug-dudx-dvdx", IMG_COLOR, -1}, {"debug-dudxy-dvdxy", IMG_COLOR, -1},
+	{"debug-dudy-dvdy", IMG_COLOR, -1}, {"debug-faces-edges", IMG_COLOR, -1}, {"debug-light-estimation-light-dirac", IMG_COLOR, -1},
+	{"debug-light-estimation-light-sampling", IMG_COLOR, -1}, {"debug-light-estimation-mat-sampling", IMG_COLOR, -1}, {"debug-nu", IMG_COLOR, -1},
+	{"debug-nv", IMG_COLOR, -1}, {"debug-objects-edges", IMG_COLOR, -1}, {"debug-sampling-factor", IMG_COLOR, -1},
+	{"debug-wireframe", IMG_COLOR_ALPHA, -1}, {"diffuse", IMG_COLOR, -1}, {"adv-diffuse-color", IMG_COLOR, LK_DIFFUSE_COLOR},
+	{"adv-diffuse-indirect", IMG_COLOR, -1}, {"diffuse-noshadow", IMG_COLOR, -1}, {"disabled", IMG_COLOR, -1}, {"emit", IMG_COLOR, -1},
+	{"env", IMG_COLOR, -1}, {"adv-glossy", IMG_COLOR, -1}, {"adv-glossy-color", IMG_COLOR, -1}, {"adv-glossy-indirect", IMG_COLOR, -1},
+	{"adv-indirect", IMG_COLOR, -1}, {"indirect", IMG_COLOR, -1}, {"mat-index-abs", IMG_GRAY, LK_MAT_INDEX_ABS}, {"mat-index-auto", IMG_COLOR, -1},
+	{"mat-index-auto-abs", IMG_COLOR, -1}, {"mat-index-mask", IMG_COLOR_ALPHA, -1}, {"mat-index-mask-all", IMG_COLOR_ALPHA, -1},
+	{"mat-index-mask-shadow", IMG_COLOR_ALPHA, -1}, {"mat-index-norm", IMG_GRAY, LK_MAT_INDEX_NORM}, {"mist", IMG_GRAY_ALPHA, LK_MIST},
+	{"debug-normal-geom", IMG_COLOR, LK_NORMAL_GEOM}, {"debug-normal-smooth", IMG_COLOR, LK_NORMAL_SMOOTH},
+	{"obj-index-abs", IMG_GRAY, LK_OBJ_INDEX_ABS}, {"obj-index-auto", IMG_COLOR, -1}, {"obj-index-auto-abs", IMG_COLOR, -1},
+	{"obj-index-mask", IMG_COLOR_ALPHA, -1}, {"obj-index-mask-all", IMG_COLOR_ALPHA, -1}, {"obj-index-mask-shadow", IMG_COLOR_ALPHA, -1},
+	{"obj-index-norm", IMG_GRAY, LK_OBJ_INDEX_NORM}, {"adv-radiance", IMG_COLOR, -1}, {"reflect", IMG_COLOR, -1}, {"adv-reflect", IMG_COLOR, -1},
+	{"refract", IMG_COLOR, -1}, {"adv-refract", IMG_COLOR, -1}, {"shadow", IMG_GRAY_ALPHA, -1}, {"adv-subsurface", IMG_COLOR, -1},
+	{"adv-subsurface-color", IMG_COLOR, -1}, {"adv-subsurface-indirect", IMG_COLOR, -1}, {"adv-surface-integration", IMG_COLOR, -1},
+	{"toon", IMG_COLOR, -1}, {"adv-trans", IMG_COLOR, -1}, {"adv-trans-color", IMG_COLOR, -1}, {"adv-trans-indirect", IMG_COLOR, -1},
+	{"debug-uv", IMG_COLOR, LK_UV}, {"adv-volume-integration", IMG_COLOR, -1}, {"adv-volume-transmittance", IMG_GRAY, -1},
+	{"z-depth-abs", IMG_GRAY_ALPHA, LK_ZDEPTH_ABS}, {"z-depth-norm", IMG_GRAY_ALPHA, LK_ZDEPTH_NORM},
+};
+constexpr int kLayerTypeCount = (int)(sizeof(kLayerTypes) / sizeof(kLayerTypes[0]));
+
+// Image::getTypeFromName / getTypeNameShort / getTypeNameLong / getNumChannels (image.cc:149-244)
+int imageTypeFromName(const std::string &n)
+{
+	if(n == "ColorAlpha") return IMG_COLOR_ALPHA;
+	if(n == "Color") return IMG_COLOR;
+	if(n == "GrayAlpha") return IMG_GRAY_ALPHA;
+	if(n == "Gray") return IMG_GRAY;
+	return IMG_NONE;
+}
+const char *imageTypeShort(int t)
+{
+	static const char *n[5] = {"unknown", "Gray", "GrayAlpha", "Color", "ColorAlpha"};
+	return n[t >= 0 && t < 5 ? t : 0];
+}
+const char *imageTypeLong(int t)
+{
+	static const char *n[5] = {"unknown image type [0 channels]", "Gray [1 channel]", "Gray + Alpha [2 channels]", "Color [3 channels]",
+	                           "Color + Alpha [4 channels]"};
+	return n[t >= 0 && t < 5 ? t : 0];
+}
+int imageTypeChannels(int t)
+{
+	static const int n[5] = {0, 1, 2, 3, 4};
+	return n[t >= 0 && t < 5 ? t : 0];
+}
+bool imageTypeHasAlpha(int t) { return t != IMG_COLOR && t != IMG_GRAY; }   // Image::hasAlpha: "none" counts as with alpha
+}   // namespace
+
+void Scene::defineLayer(const ParamMap &p)
+{
+	std::string type_name, image_type_name, exported_name, exported_type_name;
+	p.get("type", type_name);
+	p.get("image_type", image_type_name);
+	p.get("exported_image_name", exported_name);
+	p.get("exported_image_type", exported_type_name);
+	// LayerDef::getType: "disabled", "unknown", empty and unlisted names are Disabled
+	int type = -1;
+	for(int t = 0; t < kLayerTypeCount; ++t)
+		if(type_name == kLayerTypes[t].name) type = t;
+	if(type < 0 || type_name == "disabled")
+	{
+		log.warning("Scene: cannot create layer 'disabled' of unknown or disabled layer type");
+		return;
+	}
+	const LayerTypeDef &def = kLayerTypes[type];
+	if(type != 0 && def.kind < 0)
+	{
+		log.warning("Layers: layer '" + type_name + "' is not produced by the GPU core (combined only)");
+		return;
+	}
+	const int image_type = image_type_name.empty() ? def.image_type : imageTypeFromName(image_type_name);
+	const int exported_type = imageTypeFromName(exported_type_name);
+	// the layer kernels read the per-primitive attribute rows: when the first layer with an image appears (a new
+	// definition, or a redefinition that gives a layer its image), a scene built without them is built again
+	struct DirtyOnFirstLayer
+	{
+		Scene &s;
+		bool had;
+		~DirtyOnFirstLayer() { if(!had && !s.extraLayers().empty()) s.geometry_dirty = true; }
+	} dirty_guard{*this, !extraLayers().empty()};
+	auto it = layer_defs.find(type);
+	if(it != layer_defs.end())
+	{
+		// scene.cc:696-719: an internal image cannot be removed, an exported layer cannot become internal
+		LayerDesc &l = it->second;
+		if(l.image_type == image_type && l.exported_image_type == exported_type) return;
+		if(!(image_type == IMG_NONE && l.image_type != IMG_NONE)) l.image_type = image_type;
+		if(!(exported_type == IMG_NONE && l.exported_image_type != IMG_NONE))
+		{
+			l.exported_image_type = exported_type;
+			l.exported_image_name = exported_name;
+		}
+		log.info("Scene: layer redefined: " + l.name);
+		return;
+	}
+	LayerDesc l;
+	l.type = type;
+	l.kind = def.kind;
+	l.name = def.name;
+	l.image_type = image_type;
+	l.exported_image_type = exported_type;
+	l.exported_image_name = exported_name;
+	layer_defs[type] = l;
+	log.info("Scene: layer defined: " + l.name);
+}
+
+std::vector<const LayerDesc *> Scene::extraLayers() const
+{
+	std::vector<const LayerDesc *> out;
+	for(const auto &kv : layer_defs)
+		if(kv.second.kind >= 0 && kv.second.image_type != IMG_NONE) out.push_back(&kv.second);
+	return out;
+}
+
+std::string Scene::layersTable() const
+{
+	// only "combined" (defined or not): the one line of a render without layers
+	if(extraLayers().empty()) return "combined\tCombined\tColorAlpha\n";
+	std::string s;
+	auto line = [&](const std::string &exported_name, const std::string &type_name, int exported_type) {
+		s += exported_name + '\t' + type_name + '\t' + imageTypeShort(exported_type) + '\t' + std::to_string(imageTypeChannels(exported_type)) + '\t' +
+		     imageTypeLong(exported_type) + '\n';
+	};
+	// (Scene::defineBasicLayers: an undefined combined layer is ColorAlpha, exported as ColorAlpha)
+	if(!layer_defs.count(0)) line("", "combined", IMG_COLOR_ALPHA);
+	for(const auto &kv : layer_defs)
+		if(kv.second.exported()) line(kv.second.exported_image_name, kv.second.name, kv.second.exported_image_type);
+	return s;
+}
+
+bool Scene::getFilmLayer(const std::string &name, float *rgba)
+{
+	if(layer_films_stale)
+	{
+		if(!gpu()->downloadLayers(layer_films, false)) return false;
+		layer_films_stale = false;
+	}
+	const size_t plane = (size_t)film_w * film_h * 4;
+	for(size_t k = 0; k < layer_film_names.size(); ++k)
+	{
+		if(layer_film_names[k] != name || layer_films.size() < (k + 1) * plane) continue;
+		// (the image type the render used, not a later redefinition's)
+		const bool ceil_it = name == "obj-index-abs" || name == "mat-index-abs";
+		const bool alpha = k >= layer_film_alpha.size() || layer_film_alpha[k];
+		const float *src = &layer_films[k * plane];
+		for(size_t i = 0; i < plane; i += 4)
+		{
+			// imagefilm.cc:515-523 / :600-608: Rgba::ceil of the absolute index layers
+			for(int c = 0; c < 4; ++c) rgba[i + (size_t)c] = ceil_it ? std::ceil(src[i + (size_t)c]) : src[i + (size_t)c];
+			if(!alpha) rgba[i + 3] = 1.f;
+		}
+		return true;
+	}
+	return false;
+}
+
 // One primitive's surface attribute rows (texeval.h surfAttr; primitive_triangle.cc:97-176); ng: its
 // prim_ng row, a: kAttrF4 zeroed float4.  src: a source row of the instance expansion (instexpand.hip):
 // a vertex without a normal of its own is marked, the expansion writes the instance's face normal there.
@@ -1203,10 +1385,13 @@ bool Scene::gatherInstanced(HostScene &hs)
 			return false;
 		}
 		hs.segs.push_back(g);
+		// (object_instance.h:47-54: an instance reports its base's index)
+		layer_obj_seg.push_back(g.out_prim0);
+		layer_obj_seg.push_back((int)o.object_index);
 	}
 	hs.n_verts = (int)out_verts;
 	hs.n_prims = (int)out_prims;
-	if(hs.has_attr)
+	if(hs.has_attr || hs.layer_attr)
 	{
 		hs.prim_attr.assign(hs.prim_ng.size() / 4 * kAttrF4 * 4, 0.f);
 		for(const auto &so : sources)
@@ -1302,6 +1487,8 @@ bool Scene::buildAccelerator()
 	{
 		const auto t0 = std::chrono::steady_clock::now();
 		HostScene hs;
+		hs.layer_attr = !extraLayers().empty();
+		layer_obj_seg.clear();
 		materialRows(hs);   // (has_attr: a material with shader nodes)
 		if(!gatherInstanced(hs)) return false;
 		int leaf = 1, width = 4;
@@ -1335,11 +1522,17 @@ bool Scene::buildAccelerator()
 	// scene.cc:1032-1060 updateObjects: gather visible, non-base mesh primitives
 	std::vector<float> verts;
 	std::vector<int> tris, tri_mat;
+	layer_obj_seg.clear();
 	for(const std::string &name : object_order)
 	{
 		const MeshObject &o = objects[name];
 		if(o.is_base || o.visibility == "invisible") continue;
 		const int v0 = (int)(verts.size() / 3);
+		if(!o.tri_mat.empty())
+		{
+			layer_obj_seg.push_back((int)tri_mat.size());
+			layer_obj_seg.push_back((int)o.object_index);
+		}
 		verts.insert(verts.end(), o.verts.begin(), o.verts.end());
 		for(size_t t = 0; t < o.tri_mat.size(); ++t)
 		{
@@ -1384,7 +1577,8 @@ bool Scene::buildAccelerator()
 		if(o.is_base || o.visibility == "invisible") continue;
 		if(o.smooth || !o.normals.empty()) hs.has_attr = true;
 	}
-	if(hs.has_attr)
+	hs.layer_attr = !extraLayers().empty();
+	if(hs.has_attr || hs.layer_attr)
 	{
 		// per-primitive surface attributes (texeval.h surfAttr; primitive_triangle.cc:97-176)
 		hs.prim_attr.assign((size_t)hs.n_prims * kAttrF4 * 4, 0.f);
@@ -1768,6 +1962,46 @@ bool Scene::render(const Callbacks &cb, yafaray_ProgressBarCallback_t progress, 
 		S.trace_stats = trace_stats ? 1 : 0;
 		film_w = s.width;
 		film_h = s.height;
+		// ---- render layers: the defined ones beside "combined", in type order (none: nothing below changes) ----
+		const std::vector<const LayerDesc *> extra = extraLayers();
+		// what the callbacks report, in type order: the layer's name, its plane among the extra layers
+		// (-1: the combined film), Rgba::ceil on output, an image type with alpha
+		struct OutLayer { std::string name, exported_name; int plane, channels; bool ceil, alpha; };
+		std::vector<OutLayer> out_layers;
+		if(!extra.empty())
+		{
+			for(const LayerDesc *l : extra) rp.layers.kinds.push_back(l->kind);
+			for(const std::string &mn : material_order)
+			{
+				auto mi = mat_pass_index_of.find(mn);
+				rp.layers.mat_index.push_back(static_cast<float>(mi == mat_pass_index_of.end() ? 0u : mi->second));
+			}
+			rp.layers.obj_seg = layer_obj_seg;
+			rp.layers.mat_highest = static_cast<float>(highest_material_index);
+			rp.layers.obj_highest = static_cast<float>(highest_object_index);
+			rp.layers.depth_from_clip = c.far_clip > -1.f;   // integrator_tiled.cc:71
+			rp.layers.near_clip = c.near_clip;
+			rp.layers.far_clip = c.far_clip;
+			// (Scene::defineBasicLayers: an undefined combined layer is exported as ColorAlpha)
+			if(!layer_defs.count(0)) out_layers.push_back({"combined", "", -1, 4, false, true});
+			int plane = 0;
+			for(const auto &kv : layer_defs)
+			{
+				const LayerDesc &l = kv.second;
+				const bool is_extra = l.kind >= 0 && l.image_type != IMG_NONE;
+				if(l.exported() && (l.type == 0 || is_extra))
+					out_layers.push_back({l.name, l.exported_image_name, l.type == 0 ? -1 : plane, imageTypeChannels(l.exported_image_type),
+					                      l.name == "obj-index-abs" || l.name == "mat-index-abs", l.type == 0 || imageTypeHasAlpha(l.image_type)});
+				if(is_extra) ++plane;
+			}
+		}
+		// one pixel as put-pixel reports it (imagefilm.cc:513-527)
+		auto putLayerPixel = [&](const std::string &vname, const OutLayer &ol, const float *px, int x, int y) {
+			float v[4] = {px[0], px[1], px[2], px[3]};
+			if(ol.ceil) for(float &f : v) f = std::ceil(f);
+			if(!ol.alpha) v[3] = 1.f;
+			cb.put_pixel(vname.c_str(), ol.name.c_str(), x, y, v[0], v[1], v[2], v[3], cb.put_pixel_data);
+		};
 		if(!quiet)
 		{
 			std::ostringstream os;
@@ -1776,7 +2010,11 @@ bool Scene::render(const Callbacks &cb, yafaray_ProgressBarCallback_t progress, 
 			if(S.integrator == INT_PATH) os << ", bounces " << S.bounces << ", path_samples " << S.path_samples << ", rr_min " << S.rr_min_bounces;
 			log.params(os.str());
 			if(cb.notify_view) cb.notify_view(view.first.c_str(), cb.notify_view_data);
-			if(cb.notify_layer) cb.notify_layer("combined", "Combined", s.width, s.height, 4, cb.notify_layer_data);
+			// imagefilm.cc:249-256: once per exported layer
+			if(cb.notify_layer && extra.empty()) cb.notify_layer("combined", "Combined", s.width, s.height, 4, cb.notify_layer_data);
+			else if(cb.notify_layer)
+				for(const OutLayer &ol : out_layers)
+					cb.notify_layer(ol.name.c_str(), ol.exported_name.c_str(), s.width, s.height, ol.channels, cb.notify_layer_data);
 			if(progress) progress(s.width * s.height, 0, "Rendering...", progress_data);
 		}
 		// ---- film load / save (ImageFilm::init imagefilm.cc:225-241, flush :657-662, nextPass :282-286) ----
@@ -1804,11 +2042,13 @@ bool Scene::render(const Callbacks &cb, yafaray_ProgressBarCallback_t progress, 
 		{
 			film_io.weights.assign((size_t)s.width * s.height, 0.f);
 			film_io.rgba.assign((size_t)s.width * s.height * 4, 0.f);
+			film_io.layers.assign(extra.size() * (size_t)s.width * s.height * 4, 0.f);   // (a film with another layer count is refused)
 			if(filmio::loadAllInFolder(log, s.film_load_save_path, film_io))
 			{
 				rp.resumed = true;
 				rp.load_rgba = film_io.rgba.data();
 				rp.load_weights = film_io.weights.data();
+				if(!extra.empty()) rp.layers.load_accum = film_io.layers.data();
 				rp.resume_sampling_offset = film_io.sampling_offset;
 				S.base_offset = film_io.base_sampling_offset;
 				rp.film.sample_offset = S.base_offset;
@@ -1819,7 +2059,7 @@ bool Scene::render(const Callbacks &cb, yafaray_ProgressBarCallback_t progress, 
 		auto saveFilm = [&]() {
 			filmio::Film out = film_io;
 			out.sampling_offset = gpu()->samplingOffset();
-			if(gpu()->downloadAccum(out.rgba, out.weights)) filmio::save(log, film_file, out);
+			if(gpu()->downloadAccum(out.rgba, out.weights) && gpu()->downloadLayers(out.layers, true)) filmio::save(log, film_file, out);
 		};
 		int autosave_passes = 0;
 		const auto autosave_t0 = std::chrono::steady_clock::now();
@@ -1857,8 +2097,9 @@ bool Scene::render(const Callbacks &cb, yafaray_ProgressBarCallback_t progress, 
 			// render shows when the tile finishes, flushArea, progress by the tile's area
 			const int ntx = (s.width + s.tile_size - 1) / s.tile_size;
 			const std::string vname = view.first;
-			rp.on_tiles = [&, ntx, vname, order](int pass, const std::vector<float> &part) {
+			rp.on_tiles = [&, ntx, vname, order](int pass, const std::vector<float> &part, const std::vector<float> &layer_part) {
 				(void)pass;
+				const size_t lplane = (size_t)s.width * s.height * 4;
 				const int n_pix = s.width * s.height;
 				int done_px = 0;
 				for(size_t k = 0; k < order.size(); ++k)
@@ -1868,13 +2109,22 @@ bool Scene::render(const Callbacks &cb, yafaray_ProgressBarCallback_t progress, 
 					// areas in camera coordinates (imagefilm.cc:462-467, 533), pixels in film coordinates (:527)
 					if(cb.highlight_area)
 						cb.highlight_area(vname.c_str(), (int)k, tx + s.xstart, ty + s.ystart, x1 + s.xstart, y1 + s.ystart, cb.highlight_area_data);
-					if(cb.put_pixel)
+					if(cb.put_pixel && extra.empty())
 						for(int y = ty; y < y1; ++y)
 							for(int x = tx; x < x1; ++x)
 							{
 								const float *px = &part[4 * ((size_t)y * s.width + x)];
 								cb.put_pixel(vname.c_str(), "combined", x, y, px[0], px[1], px[2], px[3], cb.put_pixel_data);
 							}
+					else if(cb.put_pixel)
+						// imagefilm.cc:505-529: layer-major inside the area, the exported layers in type order
+						for(const OutLayer &ol : out_layers)
+						{
+							const float *src = ol.plane < 0 ? part.data() : layer_part.data() + (size_t)ol.plane * lplane;
+							if(ol.plane >= 0 && layer_part.size() < ((size_t)ol.plane + 1) * lplane) continue;
+							for(int y = ty; y < y1; ++y)
+								for(int x = tx; x < x1; ++x) putLayerPixel(vname, ol, src + 4 * ((size_t)y * s.width + x), x, y);
+						}
 					if(cb.flush_area) cb.flush_area(vname.c_str(), (int)k, tx + s.xstart, ty + s.ystart, x1 + s.xstart, y1 + s.ystart, cb.flush_area_data);
 					done_px += (x1 - tx) * (y1 - ty);
 					if(progress) progress(n_pix, done_px, "Rendering...", progress_data);
@@ -1929,7 +2179,17 @@ bool Scene::render(const Callbacks &cb, yafaray_ProgressBarCallback_t progress, 
 		stats = (grouped && group_world <= 1) ? group_stats_ : gpu()->stats();
 		stats.build_seconds = build;
 		film_on_gpu_only = quiet;
+		layer_film_names.clear();
+		layer_film_alpha.clear();
+		for(const LayerDesc *l : extra)
+		{
+			layer_film_names.push_back(l->name);
+			layer_film_alpha.push_back(imageTypeHasAlpha(l->image_type));
+		}
+		layer_films_stale = quiet && !extra.empty();
+		if(extra.empty()) layer_films.clear();
 		if(quiet) continue;
+		if(!extra.empty() && !gpu()->downloadLayers(layer_films, false)) return false;
 		// the flush needs the colours (putPixel); the weights stay on the GPU until getFilm asks for them
 		if(!gpu()->download(film_rgba, film_weights, s.width, s.height, true, false)) return false;
 		film_weights_stale = true;
@@ -1968,7 +2228,7 @@ bool Scene::render(const Callbacks &cb, yafaray_ProgressBarCallback_t progress, 
 				if(progress) progress(n_pix, done_px, "Rendering...", progress_data);
 			}
 		}
-		if(cb.put_pixel)
+		if(cb.put_pixel && extra.empty())
 			for(int y = 0; y < s.height; ++y)
 			{
 				if(!ownedRow(y)) continue;
@@ -1976,6 +2236,19 @@ bool Scene::render(const Callbacks &cb, yafaray_ProgressBarCallback_t progress, 
 				{
 					const float *px = &film_rgba[4 * ((size_t)y * s.width + x)];
 					cb.put_pixel(view.first.c_str(), "combined", x, y, px[0], px[1], px[2], px[3], cb.put_pixel_data);
+				}
+			}
+		else if(cb.put_pixel)
+			// imagefilm.cc:590-617: every exported layer in type order, each over the whole film
+			for(const OutLayer &ol : out_layers)
+			{
+				const size_t lplane = (size_t)s.width * s.height * 4;
+				if(ol.plane >= 0 && layer_films.size() < ((size_t)ol.plane + 1) * lplane) continue;
+				const float *src = ol.plane < 0 ? film_rgba.data() : layer_films.data() + (size_t)ol.plane * lplane;
+				for(int y = 0; y < s.height; ++y)
+				{
+					if(!ownedRow(y)) continue;
+					for(int x = 0; x < s.width; ++x) putLayerPixel(view.first, ol, src + 4 * ((size_t)y * s.width + x), x, y);
 				}
 			}
 		if(cb.flush) cb.flush(view.first.c_str(), cb.flush_data);

@@ -120,6 +120,7 @@ struct MeshObject
 	std::vector<int> tri_nidx;           // 3 normal indices per triangle (-1: face normal)
 	bool smooth = false;
 	bool is_base = false;
+	unsigned int object_index = 0;       // "object_index" (object_basic.h:44-51): the obj-index layers' value; an instance reports its base's
 	std::string visibility = "normal";
 	bool ended = false;
 };
@@ -191,6 +192,19 @@ struct Callbacks
 	yafaray_RenderHighlightAreaCallback_t highlight_area = nullptr; void *highlight_area_data = nullptr;
 };
 
+// A defined render layer (Scene::defineLayer, scene.cc:665-727; include/common/layer.h).  Image types:
+// 0 none, 1 Gray, 2 GrayAlpha, 3 Color, 4 ColorAlpha (Image::getTypeFromName).  Every layer is stored as
+// RGBA float whatever image_type says; a type without alpha reports alpha 1 on output ("Render layers").
+struct LayerDesc
+{
+	int type = 0;                  // position in the reference's LayerDef::Type order (0: combined)
+	int kind = -1;                 // LK_* (devscene.h); -1: combined
+	std::string name;              // LayerDef::getName
+	int image_type = 0, exported_image_type = 0;
+	std::string exported_image_name;
+	bool exported() const { return exported_image_type != 0; }
+};
+
 class GpuRenderer;
 struct KernelTimes;
 struct RenderParams;
@@ -221,7 +235,13 @@ class Scene
 		struct IntegratorState { uint64_t id = 0; int processing = 0; };
 		std::map<std::string, IntegratorState> integrator_state;
 		uint64_t integrator_ids_ = 0;
-		std::vector<std::string> layers;
+		// the defined layers by LayerDef::Type (std::map: the reference's order — film planes, callbacks, film file);
+		// empty until the first defineLayer: the combined layer alone, exported as ColorAlpha
+		std::map<int, LayerDesc> layer_defs;
+		std::map<std::string, unsigned int> mat_pass_index_of;   // "mat_pass_index" per material (material.h:155-166)
+		// Material::material_index_highest_ / ObjectBasic::highest_object_index_: start at 1, raised by every index set
+		unsigned int highest_material_index = 1, highest_object_index = 1;
+		std::vector<int> layer_obj_seg;                       // (first primitive, object_index) per object of the built scene
 		std::map<std::string, ParamMap> outputs;
 		std::map<std::string, std::shared_ptr<HostImage>> images;
 		std::map<std::string, int> texture_index;                 // name -> textures[]
@@ -262,6 +282,13 @@ class Scene
 		bool createIntegrator(const std::string &name, const ParamMap &p);
 		bool createRenderView(const std::string &name, const ParamMap &p);
 		bool setupRender(const ParamMap &p);
+		void defineLayer(const ParamMap &p);
+		// the layers beside "combined" that the GPU core produces, in type order (the layer planes' order)
+		std::vector<const LayerDesc *> extraLayers() const;
+		std::string layersTable() const;   // Layers::printExportedTable (layers.cc:55-67)
+		// the last render's layer `name` as put-pixel reports it (normalised, ceil() of the abs-index layers,
+		// alpha 1 for a type without alpha); "combined" is the film
+		bool getFilmLayer(const std::string &name, float *rgba);
 		bool render(const Callbacks &cb, yafaray_ProgressBarCallback_t progress, void *progress_data, bool quiet);
 		bool buildAccelerator();
 		GpuRenderer *gpu();                 // member 0 (holds the film, serves the ray seam)
@@ -276,6 +303,10 @@ class Scene
 		int film_w = 0, film_h = 0;
 		bool film_on_gpu_only = false;   // the last render was quiet: film_rgba / film_weights are stale
 		bool film_weights_stale = false; // the last flush downloaded film_rgba only (getFilm fetches the weights)
+		std::vector<float> layer_films;  // the last render's extra layers (extraLayers() order), W x H RGBA each, normalised
+		std::vector<std::string> layer_film_names;   // their type names
+		std::vector<bool> layer_film_alpha;          // ... and whether the image type they were rendered with has alpha
+		bool layer_films_stale = false;  // a quiet render left them on the GPU
 		yafaray_amd_stats_t stats{};
 
 	private:

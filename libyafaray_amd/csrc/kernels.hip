@@ -7890,3 +7890,6 @@ hipError_t yafamd_launch_trace_rays(const DevScene *S, int any, const float4 *ro
 }
 
 }
+
+// the render layers' first-hit pass and film (they call this unit's device functions)
+#include "layers_kernels.h"

@@ -112,6 +112,12 @@ hipError_t yafamd_aa_next_pass(const float4 *accum, const float *weights, int W,
                                hipStream_t st);
 hipError_t yafamd_launch_trace_rays(const DevScene *S, int any, const float4 *ro, const float4 *rd, int n, float *t_out,
                                     int *prim_out, int stack_depth, hipStream_t st);
+// render layers (layers_kernels.h)
+hipError_t yafamd_layer_depth_range(const DevScene *S, float *range, int stack_depth, hipStream_t st);
+hipError_t yafamd_launch_layer_hits(const DevScene *S, const DevLayers *L, const DevJob *jobs, int n_jobs, uint64_t chunk_base, int n, int stack_depth,
+                                    hipStream_t st);
+hipError_t yafamd_launch_layer_film(const DevFilm *F, const DevLayers *L, const float4 *prim_ng, const uint8_t *flags, float4 *accum, float4 *out,
+                                    const float *weights, int y0, int y1, float clamp_samples, int accumulate, hipStream_t st);
 }
 
 namespace
@@ -345,6 +351,11 @@ struct GpuRenderer::Impl
 	Buf samples, film, weights, jobs;
 	Buf accum, aa_flags, aa_plist;   // unnormalised film (adaptive passes add to it), nextPass flags, resampled pixels
 	int film_w = 0, film_h = 0;
+	// render layers (layers_kernels.h), allocated only by a render that defines any: first-hit records and the
+	// adv-diffuse-color plane per sample, n_layers film / accumulator planes, the partial planes of the
+	// per-tile callbacks, the index tables and the depth range
+	Buf lay_rec, lay_albedo, lay_accum, lay_film, lay_pfilm, lay_mat, lay_obj, lay_depth;
+	int n_layers = 0;
 	// chunk buffers
 	size_t slots_cap = 0;
 	bool v0_alloc = false, tree_alloc = false, ao_alloc = false;
@@ -407,6 +418,7 @@ struct GpuRenderer::Impl
 		              &weights, &jobs, &counters, &stats, &accum, &aa_flags, &aa_plist})
 			b->release();
 		for(Buf &b : chunk_bufs) b.release();
+		for(Buf *b : {&lay_rec, &lay_albedo, &lay_accum, &lay_film, &lay_pfilm, &lay_mat, &lay_obj, &lay_depth}) b->release();
 		for(Buf *b : {&g_send, &g_recv, &g_wsend, &g_wrecv, &g_times, &g_status}) b->release();
 		for(Buf *b : {&fg_ts, &g_log, &g_log_n, &walk_spill, &path_next, &lpc, &lpc_seg, &lpc_stats, &mesh_tris, &mesh_cdf, &mesh_nodes, &mesh_btris, &pre_stats, &fg_terms, &fg_longs,
 		              &fg_long_terms, &fg_long_count, &bin_keys, &bin_keys2, &bin_iota, &bin_perm, &bin_tmp, &dfr_kind, &dfr_pp,
@@ -573,16 +585,17 @@ bool GpuRenderer::expandInstances(const HostScene &hs, std::vector<float> *verts
 	if(!allocCopy(log_, segs, hs.segs.data(), hs.segs.size()) || !allocCopy(log_, sv, hs.verts.data(), hs.verts.size()) ||
 	   !allocCopy(log_, st, hs.tris.data(), hs.tris.size()) || !allocCopy(log_, sng, hs.prim_ng.data(), hs.prim_ng.size()))
 		return false;
-	if(hs.has_attr && !allocCopy(log_, sattr, hs.prim_attr.data(), hs.prim_attr.size())) return false;
+	const bool attr_rows = hs.has_attr || hs.layer_attr;   // (the render layers read the rows of a scene that has none of its own)
+	if(attr_rows && !allocCopy(log_, sattr, hs.prim_attr.data(), hs.prim_attr.size())) return false;
 	const size_t nv = (size_t)hs.n_verts, np = (size_t)hs.n_prims;
 	bool ok = ensure(log_, bounds, 6 * sizeof(float)) && ensure(log_, d.world_verts, nv * 3 * sizeof(float)) &&
 	          ensure(log_, d.world_tris, np * 3 * sizeof(int)) && ensure(log_, d.prim_ng, np * sizeof(float4));
-	if(ok && hs.has_attr) ok = ensure(log_, d.prim_attr, np * kAttrF4 * sizeof(float4));
+	if(ok && attr_rows) ok = ensure(log_, d.prim_attr, np * kAttrF4 * sizeof(float4));
 	hipError_t e = hipSuccess;
 	if(ok)
 		e = yafamd_instance_expand((const DevInstSeg *)segs.p, (int)hs.segs.size(), (const float *)sv.p, (const int *)st.p, (const float4 *)sng.p,
-		                           hs.has_attr ? (const float4 *)sattr.p : nullptr, hs.n_verts, hs.n_prims, (float *)d.world_verts.p, (int *)d.world_tris.p,
-		                           (float4 *)d.prim_ng.p, hs.has_attr ? (float4 *)d.prim_attr.p : nullptr, (float *)bounds.p, d.stream);
+		                           attr_rows ? (const float4 *)sattr.p : nullptr, hs.n_verts, hs.n_prims, (float *)d.world_verts.p, (int *)d.world_tris.p,
+		                           (float4 *)d.prim_ng.p, attr_rows ? (float4 *)d.prim_attr.p : nullptr, (float *)bounds.p, d.stream);
 	float b6[6] = {};
 	if(ok && e == hipSuccess) e = hipMemcpy(b6, bounds.p, sizeof(b6), hipMemcpyDeviceToHost);
 	if(ok && e == hipSuccess && verts)
@@ -736,14 +749,20 @@ bool GpuRenderer::upload(HostScene &hs)
 	else for(Buf *b : {&d.mesh_tris, &d.mesh_cdf, &d.mesh_nodes, &d.mesh_btris}) b->release();
 	d.has_attr = hs.has_attr;
 	d.n_textures = (int)hs.textures.size();
-	if(hs.has_attr)
+	// the attribute rows: the scene's own (has_attr: k_surface reads them) or for the render layers only
+	// (layer_attr: the wavefront does not see them, S.has_attr stays 0)
+	if(hs.has_attr || hs.layer_attr)
 	{
 		if(!hs.instanced && !allocCopy(log_, d.prim_attr, hs.prim_attr.data(), hs.prim_attr.size())) return false;
+	}
+	else d.prim_attr.release();
+	if(hs.has_attr)
+	{
 		if(!allocCopy(log_, d.shader_nodes, hs.shader_nodes.data(), hs.shader_nodes.size())) return false;
 		if(!allocCopy(log_, d.textures, hs.textures.data(), hs.textures.size())) return false;
 		if(!allocCopy(log_, d.texels, hs.texels.data(), hs.texels.size())) return false;
 	}
-	else for(Buf *b : {&d.prim_attr, &d.shader_nodes, &d.textures, &d.texels}) b->release();
+	else for(Buf *b : {&d.shader_nodes, &d.textures, &d.texels}) b->release();
 	d.n_nodes = hs.bvh.n_nodes;
 	d.n_tris = hs.n_prims;
 	d.n_mats = (int)hs.mats.size();
@@ -1910,6 +1929,109 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		HIPCHECK(hipMemcpyAsync(d.weights.p, rp.load_weights, (size_t)W * H * sizeof(float), hipMemcpyHostToDevice, d.stream));
 		HIPCHECK(hipStreamSynchronize(d.stream));
 	}
+	// ---- render layers (layers_kernels.h): only a render that defines any allocates or launches anything ----
+	const int n_lay = (int)rp.layers.kinds.size();
+	DevLayers LY{};
+	d.n_layers = n_lay;
+	uint64_t layer_rays = 0;   // closest rays of the first-hit pass and of the depth pre-pass
+	const size_t lay_plane = (size_t)W * H * sizeof(float4);
+	const bool lay_tiles = n_lay > 0 && (bool)rp.on_tiles && rp.shard_world == 1 && groupWorld() <= 1;
+	if(n_lay > LK_COUNT)
+	{
+		log_.error("Layers: more layers than the GPU core produces");
+		return false;
+	}
+	// layer buffers that are not allocated yet (or too small) have to fit the free device memory
+	auto ensureLayerBufs = [&](std::initializer_list<std::pair<Buf *, size_t>> want) -> bool {
+		size_t fresh = 0;
+		for(const auto &w : want)
+			if(w.second && !(w.first->p && w.first->bytes >= w.second)) fresh += w.second;
+		size_t free_b = 0, total_b = 0;
+		if(fresh && hipMemGetInfo(&free_b, &total_b) == hipSuccess && fresh > free_b)
+		{
+			log_.error("Layers: the layer buffers (" + std::to_string(fresh >> 20) + " MB) exceed the free device memory (" + std::to_string(free_b >> 20) +
+			           " MB); define fewer layers or render fewer samples per pass");
+			return false;
+		}
+		for(const auto &w : want)
+			if(w.second && !ensure(log_, *w.first, w.second)) return false;
+		return true;
+	};
+	// a render without layers keeps none of an earlier render's layer buffers
+	if(n_lay == 0)
+		for(Buf *b : {&d.lay_rec, &d.lay_albedo, &d.lay_accum, &d.lay_film, &d.lay_pfilm, &d.lay_mat, &d.lay_obj, &d.lay_depth}) b->release();
+	if(n_lay > 0)
+	{
+		// The first-hit pass and the depth pre-pass keep the whole traversal stack in LDS (k_trace_rays' context,
+		// no spill column): a BVH whose stack bound does not fit is refused here, not at the launch
+		if((size_t)d.stack_depth * (size_t)yafamd_trace_block() * sizeof(int) > (size_t)64 * 1024)
+		{
+			log_.error("Layers: the BVH's traversal stack bound (" + std::to_string(d.stack_depth) + " levels) exceeds the LDS stack of the layers' first-hit pass");
+			return false;
+		}
+		bool want_albedo = false, want_depth = false;
+		for(int k = 0; k < n_lay; ++k)
+		{
+			LY.kind[k] = rp.layers.kinds[(size_t)k];
+			want_albedo = want_albedo || LY.kind[k] == LK_DIFFUSE_COLOR;
+			want_depth = want_depth || LY.kind[k] == LK_ZDEPTH_NORM || LY.kind[k] == LK_MIST;
+		}
+		LY.n = n_lay;
+		if(!d.prim_attr.p)
+		{
+			log_.error("Layers: the scene was built without the layers' primitive attributes");
+			return false;
+		}
+		// (the chunk buffers come after)
+		{
+			const size_t per_sample = (size_t)W * H * spp * sizeof(float4);
+			if(!ensureLayerBufs({{&d.lay_rec, per_sample}, {&d.lay_albedo, want_albedo ? per_sample : 0}, {&d.lay_accum, n_lay * lay_plane},
+			                     {&d.lay_film, n_lay * lay_plane}, {&d.lay_pfilm, lay_tiles ? n_lay * lay_plane : 0}}))
+				return false;
+			if(!want_albedo) d.lay_albedo.release();
+			if(!lay_tiles) d.lay_pfilm.release();
+		}
+		HIPCHECK(hipMemsetAsync(d.lay_accum.p, 0, n_lay * lay_plane, d.stream));
+		HIPCHECK(hipMemsetAsync(d.lay_film.p, 0, n_lay * lay_plane, d.stream));
+		if(rp.layers.load_accum)
+		{
+			HIPCHECK(hipMemcpyAsync(d.lay_accum.p, rp.layers.load_accum, n_lay * lay_plane, hipMemcpyHostToDevice, d.stream));
+			HIPCHECK(hipStreamSynchronize(d.stream));
+		}
+		// index tables (never empty: a hit always finds its object's segment)
+		std::vector<float> mat_index = rp.layers.mat_index;
+		if(mat_index.size() < (size_t)std::max(1, d.n_mats)) mat_index.resize((size_t)std::max(1, d.n_mats), 0.f);
+		std::vector<int> obj_seg = rp.layers.obj_seg;
+		if(obj_seg.size() < 2) obj_seg = {0, 0};
+		if(!allocCopy(log_, d.lay_mat, mat_index.data(), mat_index.size()) || !allocCopy(log_, d.lay_obj, obj_seg.data(), obj_seg.size())) return false;
+		LY.prim_attr = (const float4 *)d.prim_attr.p;
+		LY.mat_index = (const float *)d.lay_mat.p;
+		LY.obj_seg = (const int2 *)d.lay_obj.p;
+		LY.n_obj_seg = (int)(obj_seg.size() / 2);
+		LY.n_prims = d.n_tris;
+		LY.n_mats = (int)mat_index.size();
+		LY.mat_highest = rp.layers.mat_highest;
+		LY.obj_highest = rp.layers.obj_highest;
+		LY.rec = (float4 *)d.lay_rec.p;
+		LY.albedo = want_albedo ? (float4 *)d.lay_albedo.p : nullptr;
+		if(want_depth)
+		{
+			// TiledIntegrator::precalcDepths (integrator_tiled.cc:69-95); every group member computes the same pair
+			if(!ensure(log_, d.lay_depth, 2 * sizeof(float))) return false;
+			if(rp.layers.depth_from_clip)
+			{
+				float range[2] = {rp.layers.near_clip, rp.layers.far_clip};
+				if(range[1] > 0.f) range[1] = 1.f / (range[1] - range[0]);
+				HIPCHECK(hipMemcpy(d.lay_depth.p, range, sizeof(range), hipMemcpyHostToDevice));
+			}
+			else
+			{
+				PROF(KK_LAYER_HITS, yafamd_layer_depth_range(&S, (float *)d.lay_depth.p, d.stack_depth, d.stream));
+				layer_rays += (uint64_t)std::max(0, S.cam.resx) * (uint64_t)std::max(0, S.cam.resy);
+			}
+			LY.depth = (const float *)d.lay_depth.p;
+		}
+	}
 	// ---- chunk buffers ----
 	size_t M = (size_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)rp.chunk_slots, std::max<uint64_t>(total, 1)));
 	// a group member's band moves from frame to frame (rebalanceBands): the chunk buffers hold twice an equal
@@ -2576,6 +2698,26 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		return ok2;
 	};
 
+	// The layers' first-hit pass over the `n_done` samples a pass rendered, chunk by chunk in the pass's own
+	// enumeration (the camera rays are regenerated: sampleAt / cameraRay with the pass's S), and the layer film
+	// beside every k_film launch (before it: k_film writes the weights both read)
+	auto runLayerHits = [&](uint64_t n_done) -> bool {
+		if(n_lay == 0) return true;
+		for(uint64_t base = 0; base < n_done; base += M)
+		{
+			const int n = (int)std::min<uint64_t>(M, n_done - base);
+			PROF(KK_LAYER_HITS, yafamd_launch_layer_hits(&S, &LY, (const DevJob *)d.jobs.p, n_jobs, base, n, d.stack_depth, d.stream));
+		}
+		layer_rays += n_done;
+		return true;
+	};
+	auto layerFilm = [&](const DevFilm &F, const uint8_t *flags, void *out, int y0, int y1, int accumulate) -> bool {
+		if(n_lay == 0) return true;
+		PROF(KK_LAYER_FILM, yafamd_launch_layer_film(&F, &LY, (const float4 *)d.prim_ng.p, flags, (float4 *)d.lay_accum.p, (float4 *)out,
+		                                             (const float *)d.weights.p, y0, y1, S.clamp_samples, accumulate, d.stream));
+		return true;
+	};
+
 	// ---- pass 0 (every pixel), then the adaptive passes (TiledIntegrator::render, integrator_tiled.cc:172-231) ----
 	const int passes = std::max(1, rp.aa.passes);
 	S.aa_multipass = passes > 1 ? 1 : 0;
@@ -2600,10 +2742,12 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		Fp.partial = 1;
 		PROF(KK_FILM, yafamd_launch_film(&Fp, (const float4 *)d.samples.p, flags, (float4 *)d.accum.p, (float4 *)d.pfilm.p, (float *)d.weights.p, 0, H,
 		                            S.clamp_samples, accumulate, d.stream));
-		std::vector<float> host((size_t)W * H * 4);
+		if(!layerFilm(Fp, flags, d.lay_pfilm.p, 0, H, accumulate)) return false;
+		std::vector<float> host((size_t)W * H * 4), host_layers((size_t)n_lay * W * H * 4);
 		HIPCHECK(hipMemcpyAsync(host.data(), d.pfilm.p, host.size() * sizeof(float), hipMemcpyDeviceToHost, d.stream));
+		if(n_lay > 0) HIPCHECK(hipMemcpyAsync(host_layers.data(), d.lay_pfilm.p, host_layers.size() * sizeof(float), hipMemcpyDeviceToHost, d.stream));
 		HIPCHECK(hipStreamSynchronize(d.stream));
-		rp.on_tiles(pass, host);
+		rp.on_tiles(pass, host, host_layers);
 		return true;
 	};
 	uint64_t samples_total = total;
@@ -2613,14 +2757,18 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		DevFilm F0 = rp.film;
 		F0.spp = 0;
 		for(const auto &r : owned_rows_)
+		{
+			if(!layerFilm(F0, nullptr, d.lay_film.p, r.first, r.second, 1)) return false;
 			PROF(KK_FILM, yafamd_launch_film(&F0, (const float4 *)d.samples.p, nullptr, (float4 *)d.accum.p, (float4 *)d.film.p,
 			                            (float *)d.weights.p, r.first, r.second, S.clamp_samples, 1, d.stream));
+		}
 		samples_total = 0;
 		sampling_offset_ = rp.resume_sampling_offset;
 	}
 	else
 	{
 		if(!runPass(total, spp)) return false;
+		if(!runLayerHits(done)) return false;
 		const uint8_t *done_flags = nullptr;
 		if(done < total)
 		{
@@ -2634,8 +2782,11 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		}
 		if(done == total && !emitTiles(0, nullptr, 0)) return false;
 		for(const auto &r : owned_rows_)
+		{
+			if(!layerFilm(rp.film, done_flags, d.lay_film.p, r.first, r.second, 0)) return false;
 			PROF(KK_FILM, yafamd_launch_film(&rp.film, (const float4 *)d.samples.p, done_flags, (float4 *)d.accum.p, (float4 *)d.film.p,
 			                            (float *)d.weights.p, r.first, r.second, S.clamp_samples, 0, d.stream));
+		}
 		// renderPass sets the sampling offset before its workers start (integrator_tiled.cc:244), so a
 		// canceled pass advances it too
 		sampling_offset_ = (uint32_t)spp;
@@ -2734,13 +2885,25 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 				rp.film.sample_offset = S.base_offset + (uint32_t)acum;
 				const uint64_t n_total = (uint64_t)resampled_local * (uint64_t)n_pass;
 				if(!runPass(n_total, n_pass)) return false;
+				if(n_lay > 0)
+				{
+					// the pass's records (and albedo plane) in the pass's sample indexing
+					const size_t per_sample = (size_t)W * H * n_pass * sizeof(float4);
+					if(!ensureLayerBufs({{&d.lay_rec, per_sample}, {&d.lay_albedo, LY.albedo ? per_sample : 0}})) return false;
+					LY.rec = (float4 *)d.lay_rec.p;
+					if(LY.albedo) LY.albedo = (float4 *)d.lay_albedo.p;
+					if(!runLayerHits(done)) return false;
+				}
 				if(done < n_total)
 					HIPCHECK(yafamd_launch_done_flags(&S, (const DevJob *)d.jobs.p, n_jobs, (uint32_t)resampled_local, (uint32_t)(done / (uint64_t)n_pass),
 					                                  (uint8_t *)d.aa_flags.p, d.stream));
 				if(done == n_total && !emitTiles(passes_done_, (const uint8_t *)d.aa_flags.p, 1)) return false;
 				for(const auto &r : owned_rows_)
+				{
+					if(!layerFilm(rp.film, (const uint8_t *)d.aa_flags.p, d.lay_film.p, r.first, r.second, 1)) return false;
 					PROF(KK_FILM, yafamd_launch_film(&rp.film, (const float4 *)d.samples.p, (const uint8_t *)d.aa_flags.p, (float4 *)d.accum.p,
 					                            (float4 *)d.film.p, (float *)d.weights.p, r.first, r.second, S.clamp_samples, 1, d.stream));
+				}
 				samples_total += done / (uint64_t)n_pass * (uint64_t)n_pass;
 				sampling_offset_ = (uint32_t)(acum + n_pass);   // renderPass: setSamplingOffset(offset + samples), :244
 				if(done < n_total)
@@ -2809,7 +2972,7 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 			d.pre_stats_valid = false;   // counted once: a reused radiance map is not pre-gathered again
 		}
 	}
-	stats_.closest_rays = hs.closest_rays;
+	stats_.closest_rays = hs.closest_rays + layer_rays;   // (the layers' first-hit pass and depth pre-pass: one ray each)
 	stats_.shadow_rays = hs.shadow_rays;
 	stats_.node_visits = hs.node_visits;
 	stats_.tri_tests = hs.tri_tests;
@@ -2830,6 +2993,8 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		}
 		ktimes_.items[KK_CAMERA] = samples_total;
 		ktimes_.items[KK_FILM] = samples_total;
+		ktimes_.items[KK_LAYER_HITS] = layer_rays;
+		ktimes_.items[KK_LAYER_FILM] = n_lay > 0 ? samples_total : 0;
 		ktimes_.items[KK_TRACE] = hs.closest_rays + hs.shadow_rays;
 		ktimes_.items[KK_PATH] = ktimes_.launches[KK_PATH] ? samples_total : 0;
 		ktimes_.items[KK_SHADE] = hs.shade_entries;
@@ -2912,6 +3077,22 @@ bool GpuRenderer::downloadAccum(std::vector<float> &rgba, std::vector<float> &we
 	HIPCHECK(hipStreamSynchronize(d.stream));
 	HIPCHECK(hipMemcpy(rgba.data(), d.accum.p, rgba.size() * 4, hipMemcpyDeviceToHost));
 	HIPCHECK(hipMemcpy(weights.data(), d.weights.p, weights.size() * 4, hipMemcpyDeviceToHost));
+	return true;
+}
+
+int GpuRenderer::layerCount() const { return d_->n_layers; }
+
+bool GpuRenderer::downloadLayers(std::vector<float> &rgba, bool accum)
+{
+	DeviceGuard guard(device_);
+	Impl &d = *d_;
+	const Buf &src = accum ? d.lay_accum : d.lay_film;
+	const size_t n = (size_t)d.n_layers * d.film_w * d.film_h * 4;
+	rgba.resize(n);
+	if(n == 0) return true;
+	if(!src.p || src.bytes < n * sizeof(float)) { log_.error("GPU: no layer film to download"); return false; }
+	HIPCHECK(hipStreamSynchronize(d.stream));
+	HIPCHECK(hipMemcpy(rgba.data(), src.p, n * sizeof(float), hipMemcpyDeviceToHost));
 	return true;
 }
 
@@ -3078,6 +3259,13 @@ bool GpuRenderer::exchangeRows(const std::vector<int> &bounds, int what, bool to
 				if(what & XR_FILM) ok = ok && pull(d.film.p, o.film.p, row4);
 				if(what & XR_ACCUM) ok = ok && pull(d.accum.p, o.accum.p, row4);
 				if(what & (XR_FILM | XR_ACCUM)) ok = ok && pull(d.weights.p, o.weights.p, row1);
+				// the layer planes travel with the film they belong to (same rows, one plane per layer)
+				for(int l = 0; l < d.n_layers && l < o.n_layers; ++l)
+				{
+					const size_t plane = (size_t)l * H * row4;
+					if(what & XR_FILM) ok = ok && pull((char *)d.lay_film.p + plane, (const char *)o.lay_film.p + plane, row4);
+					if(what & XR_ACCUM) ok = ok && pull((char *)d.lay_accum.p + plane, (const char *)o.lay_accum.p + plane, row4);
+				}
 			}
 		ok = ok && hipStreamSynchronize(d.stream) == hipSuccess;
 		if(!ok) log_.error("GPU group: band copy between members failed");
@@ -3101,24 +3289,31 @@ bool GpuRenderer::exchangeRows(const std::vector<int> &bounds, int what, bool to
 	for(int kind : kinds)
 	{
 		if(!(what & kind)) continue;
-		void *src4 = kind == XR_FILM ? d.film.p : d.accum.p;
-		if(y1 > y0)
+		// plane -1: the combined film with the weights; then the layer planes through the same slots
+		// (every member defines the same layers: they render the same scene)
+		for(int pl = -1; pl < d.n_layers; ++pl)
 		{
-			HIPCHECK(hipMemcpyAsync(d.g_send.p, (char *)src4 + row4 * y0, row4 * (y1 - y0), hipMemcpyDeviceToDevice, d.stream));
-			HIPCHECK(hipMemcpyAsync(d.g_wsend.p, (char *)d.weights.p + row1 * y0, row1 * (y1 - y0), hipMemcpyDeviceToDevice, d.stream));
-		}
-		NCCLCHECK(ncclGroupStart());
-		NCCLCHECK(ncclAllGather(d.g_send.p, d.g_recv.p, band_px * 4, ncclFloat32, d.comm, d.stream));
-		NCCLCHECK(ncclAllGather(d.g_wsend.p, d.g_wrecv.p, band_px, ncclFloat32, d.comm, d.stream));
-		NCCLCHECK(ncclGroupEnd());
-		for(int r = 0; r < world; ++r)
-		{
-			const int a = bounds[r], b = bounds[r + 1];
-			if(b <= a || r == me) continue;
-			HIPCHECK(hipMemcpyAsync((char *)src4 + row4 * a, (char *)d.g_recv.p + (size_t)r * band_px * sizeof(float4), row4 * (b - a),
-			                        hipMemcpyDeviceToDevice, d.stream));
-			HIPCHECK(hipMemcpyAsync((char *)d.weights.p + row1 * a, (char *)d.g_wrecv.p + (size_t)r * band_px * sizeof(float), row1 * (b - a),
-			                        hipMemcpyDeviceToDevice, d.stream));
+			void *src4 = kind == XR_FILM ? d.film.p : d.accum.p;
+			if(pl >= 0) src4 = (char *)(kind == XR_FILM ? d.lay_film.p : d.lay_accum.p) + (size_t)pl * H * row4;
+			if(y1 > y0)
+			{
+				HIPCHECK(hipMemcpyAsync(d.g_send.p, (char *)src4 + row4 * y0, row4 * (y1 - y0), hipMemcpyDeviceToDevice, d.stream));
+				if(pl < 0) HIPCHECK(hipMemcpyAsync(d.g_wsend.p, (char *)d.weights.p + row1 * y0, row1 * (y1 - y0), hipMemcpyDeviceToDevice, d.stream));
+			}
+			NCCLCHECK(ncclGroupStart());
+			NCCLCHECK(ncclAllGather(d.g_send.p, d.g_recv.p, band_px * 4, ncclFloat32, d.comm, d.stream));
+			if(pl < 0) NCCLCHECK(ncclAllGather(d.g_wsend.p, d.g_wrecv.p, band_px, ncclFloat32, d.comm, d.stream));
+			NCCLCHECK(ncclGroupEnd());
+			for(int r = 0; r < world; ++r)
+			{
+				const int a = bounds[r], b = bounds[r + 1];
+				if(b <= a || r == me) continue;
+				HIPCHECK(hipMemcpyAsync((char *)src4 + row4 * a, (char *)d.g_recv.p + (size_t)r * band_px * sizeof(float4), row4 * (b - a),
+				                        hipMemcpyDeviceToDevice, d.stream));
+				if(pl < 0)
+					HIPCHECK(hipMemcpyAsync((char *)d.weights.p + row1 * a, (char *)d.g_wrecv.p + (size_t)r * band_px * sizeof(float), row1 * (b - a),
+					                        hipMemcpyDeviceToDevice, d.stream));
+			}
 		}
 	}
 	if(what & XR_TIMES)

@@ -48,6 +48,7 @@ struct HostScene
 	int n_verts = 0;                     // output vertices (instanced only)
 	// surface attributes / textures / shader nodes (texeval.h), only when has_attr
 	bool has_attr = false;
+	bool layer_attr = false;             // render layers are defined: prim_attr is built and uploaded even without has_attr
 	std::vector<float> prim_attr;        // kAttrF4 float4 per primitive
 	std::vector<DevNode> shader_nodes;
 	std::vector<DevTexture> textures;
@@ -98,13 +99,14 @@ struct AaParams
 enum KernelKind : int
 {
 	KK_CAMERA = 0, KK_TRACE, KK_SURFACE, KK_TSHADOW, KK_SHADE, KK_NEE, KK_GATHER, KK_SPAWN, KK_COMBINE, KK_FILM, KK_AA,
-	KK_PHOTON_EMIT, KK_PHOTON_BOUNCE, KK_PHOTON_COMPACT, KK_PHOTON_TREE, KK_FG, KK_PREGATHER, KK_GATHER_WALK, KK_PATH, KK_DFR, KK_COUNT
+	KK_PHOTON_EMIT, KK_PHOTON_BOUNCE, KK_PHOTON_COMPACT, KK_PHOTON_TREE, KK_FG, KK_PREGATHER, KK_GATHER_WALK, KK_PATH, KK_DFR,
+	KK_LAYER_HITS, KK_LAYER_FILM, KK_COUNT
 };
 inline const char *kernelKindName(int k)
 {
 	static const char *n[KK_COUNT] = {"k_camera", "k_trace", "k_surface", "k_tshadow", "k_shade", "k_nee", "k_gather", "k_spawn",
 	                                  "k_combine", "k_film", "aa_next_pass", "k_photon_emit", "k_photon_bounce", "photon_compact",
-	                                  "pkd_build", "k_fg", "k_pregather", "k_gather_walk", "k_path", "k_dfr"};
+	                                  "pkd_build", "k_fg", "k_pregather", "k_gather_walk", "k_path", "k_dfr", "k_layer_hits", "k_layer_film"};
 	return (k >= 0 && k < KK_COUNT) ? n[k] : "";
 }
 struct KernelTimes
@@ -115,9 +117,24 @@ struct KernelTimes
 	                                 // requests (nee), queries (gather), photon paths (emit, bounce), photons (tree)
 };
 
+// The render layers of a render that defines any beside "combined" (layers_kernels.h; Scene::defineLayer):
+// the defined kinds in type order and what their values need beside the scene.
+struct LayerParams
+{
+	std::vector<int> kinds;              // LK_*, ascending; empty: the combined layer only (no layer pass, no layer buffers)
+	std::vector<float> mat_index;        // mat_pass_index per material, creation order (DevScene::mats' order)
+	std::vector<int> obj_seg;            // (first primitive, object_index) per object, ascending first primitive
+	float mat_highest = 1.f, obj_highest = 1.f;
+	// precalcDepths (integrator_tiled.cc:69-95): the camera's clip distances when farClip > -1, else the pre-pass
+	bool depth_from_clip = false;
+	float near_clip = 0.f, far_clip = -1.f;
+	const float *load_accum = nullptr;   // resumed render: the loaded layer accumulators, kinds.size() planes of W x H RGBA
+};
+
 struct RenderParams
 {
 	DevScene scene;                      // pointers filled by the renderer
+	LayerParams layers;
 	PhotonParams pm;
 	AaParams aa;
 	DevFilm film;
@@ -143,8 +160,9 @@ struct RenderParams
 	std::vector<uint32_t> tile_rank;
 	// per-pass hook for the per-tile callbacks (ImageFilm::finishArea, imagefilm.cc:489-568): the
 	// pass's partial film (RGBA, W x H) — each pixel as the one-thread render shows it when its tile
-	// finishes.  Single GPU, uncanceled passes.
-	std::function<void(int pass, const std::vector<float> &partial)> on_tiles;
+	// finishes.  Single GPU, uncanceled passes.  layer_partial: the same for the defined layers, one
+	// W x H RGBA plane each in type order (empty: combined only).
+	std::function<void(int pass, const std::vector<float> &partial, const std::vector<float> &layer_partial)> on_tiles;
 	// Group render (the film split into contiguous row bands over the members of a device group or
 	// a render group, GpuRenderer::renderMember): the members' band boundaries (world + 1 rows; this
 	// member is shard_rank).  Empty: not a group render.  Between adaptive passes the members agree
@@ -209,6 +227,9 @@ class GpuRenderer
 		// one stream sync, DMA into pinned memory; either part can be skipped
 		bool download(PinnedFloats &rgba, PinnedFloats &weights, int w, int h, bool with_rgba = true, bool with_weights = true);
 		bool filmToDevice(void *dst, int y0, int y1);
+		// the layer planes of the last render (LayerParams::kinds' order, W x H RGBA each): normalised / accumulators
+		int layerCount() const;
+		bool downloadLayers(std::vector<float> &rgba, bool accum);
 		bool traceRays(bool any, const float *rays, int n, float *t, int *prim);
 		bool buildPhotonMap(RenderParams &rp);
 		bool buildRadianceMap(RenderParams &rp);

@@ -49,6 +49,7 @@ class Material:
     diffuse_brdf: str = "lambert"          # "oren_nayar" (material_shiny_diffuse.cc:561-571)
     sigma: float = 0.1                     # Oren-Nayar roughness
     additionaldepth: int = 0               # extra recursiveRaytrace depth (integrator_montecarlo.cc:923)
+    mat_pass_index: int = 0                # the mat-index layers' value (material.h:155-166); shinydiffusemat only
     # full typed parameter map {key: (kind, value)} (kinds s f i b v c m) and the pushed shader-node
     # lists, as a reference client passes them (tests/test01/test01.c:268-650); when set, apply()
     # issues exactly these instead of the fields above
@@ -205,6 +206,7 @@ class Object:
     has_orco: bool = True                  # with SceneSpec.orco: addVertexWithOrco (else addVertex)
     is_base: bool = False                  # "is_base_object": shows only through its instances
     visibility: str = "normal"             # or "invisible" (hides the object and its instances)
+    object_index: int = 0                  # the obj-index layers' value (object_basic.h:44-51); instances report their base's
 
 
 @dataclass
@@ -227,6 +229,9 @@ class SceneSpec:
     textures: List[TextureSpec] = field(default_factory=list)
     # object instances: (base object name, (3, 4) or (4, 4) float32 obj_to_world), added after the objects
     instances: list = field(default_factory=list)
+    # render layers beside "combined" (yafaray_defineLayer): dicts with "type" and optionally "image_type",
+    # "exported_image_type", "exported_image_name"; with any, "combined" is defined as an exported ColorAlpha layer
+    layers: list = field(default_factory=list)
 
     def render_lights(self):
         """Lights in the order the integrators see them: by name (render_view.cc:61, std::map)."""
@@ -542,6 +547,8 @@ def apply(spec: SceneSpec, api) -> None:
                 api.paramsSetFloat("sigma", m.sigma)
             if m.additionaldepth:
                 api.paramsSetInt("additionaldepth", m.additionaldepth)
+            if m.mat_pass_index:
+                api.paramsSetInt("mat_pass_index", m.mat_pass_index)
         api.createMaterial(m.name)
     api.paramsClearAll()
     for l in spec.lights:
@@ -580,6 +587,8 @@ def apply(spec: SceneSpec, api) -> None:
             api.paramsSetBool("is_base_object", True)
         if o.visibility != "normal":
             api.paramsSetString("visibility", o.visibility)
+        if o.object_index:
+            api.paramsSetInt("object_index", o.object_index)
         api.createObject(o.name)
         if use_orco:
             for v, oc in zip(spec.verts[o.v0:o.v0 + o.nv], spec.orco[o.v0:o.v0 + o.nv]):
@@ -703,7 +712,16 @@ def apply(spec: SceneSpec, api) -> None:
     api.paramsClearAll()
     api.paramsSetString("type", "combined")
     api.paramsSetString("image_type", "ColorAlpha")
+    if spec.layers:
+        api.paramsSetString("exported_image_type", "ColorAlpha")
+        api.paramsSetString("exported_image_name", "Combined")
     api.defineLayer()
+    for layer in spec.layers:
+        api.paramsClearAll()
+        for k in ("type", "image_type", "exported_image_type", "exported_image_name"):
+            if layer.get(k) is not None:
+                api.paramsSetString(k, layer[k])
+        api.defineLayer()
     api.paramsClearAll()
     api.paramsSetString("integrator_name", "default")
     if spec.background is not None:
