@@ -2266,9 +2266,11 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		return true;
 	};
 	if(!ensure(log_, d.counters, 2 * 4 * R * sizeof(uint32_t))) return false;
-	if(!ensure(log_, d.stats, sizeof(DevStats) * (size_t)d.trace_grid)) return false;
+	// two ranges of trace_grid records: [0, trace_grid) for every launch of the render's ordered sequence, and
+	// [trace_grid, 2 trace_grid) for a shadow part that runs beside the closest part (below); summed on the host
+	if(!ensure(log_, d.stats, sizeof(DevStats) * 2 * (size_t)d.trace_grid)) return false;
 	HIPCHECK(hipMemsetAsync(d.counters.p, 0, 2 * 4 * R * sizeof(uint32_t), d.stream));
-	HIPCHECK(hipMemsetAsync(d.stats.p, 0, sizeof(DevStats) * (size_t)d.trace_grid, d.stream));
+	HIPCHECK(hipMemsetAsync(d.stats.p, 0, sizeof(DevStats) * 2 * (size_t)d.trace_grid, d.stream));
 	DevCounters cnt[2];
 	for(int q = 0; q < 2; ++q)
 	{
@@ -2291,7 +2293,8 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 	}
 	// The overlapped schedule (YAFARAY_AMD_OVERLAP): the closest rays of iteration it + 1 depend
 	// on k_shade(it) only, so they are traced on the side stream while k_nee(it) fills the shadow queue on the
-	// render stream; the shadow rays of it + 1 follow on the render stream once both are done.  The films, the
+	// render stream; the shadow rays of it + 1 follow on the render stream (once both are done, or right behind
+	// k_nee: YAFARAY_AMD_OVERLAP_SHADOW below).  The films, the
 	// weights and the statistics are those of the serial schedule.  The render is eligible when k_trace runs its
 	// plain loop over an LDS-resident scene (the refill loops, the sorted windows and the brute-force kernel do
 	// not split by ray kind) and nothing else sits between k_shade and the next k_trace: no ray binning, no
@@ -2313,6 +2316,24 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_TRACE_GRID"); e && atoi(e) > 0)
 		ov_trace_grid = (int)S.n_seg * std::max(1, std::min(atoi(e), d.trace_grid) / (int)S.n_seg);
 	overlap = overlap && S.scene_in_lds && !S.ray_sort && !S.brute && !ray_bin && !S.tree && !S.tr_shad && !S.has_attr && nee_trace_stack == 0;
+	// The shadow part beside the closest part (YAFARAY_AMD_OVERLAP_SHADOW): the shadow rays of iteration it + 1
+	// depend on k_nee(it) only, and share nothing with the closest part on the side stream (sh_o / sh_d /
+	// n_shadow -> P.occ against ray_o / ray_d / n_active -> hit_t / hit_prim).  So their k_trace follows k_nee(it)
+	// on the render stream at once, and the render stream waits for the side stream after that launch instead of
+	// before it — still ahead of k_shade(it + 1), the first reader of the hits.  Two k_trace launches then run at
+	// the same time: the early shadow part counts into the second range of d.stats, and the render needs a stack
+	// without a spill column (both launches would index the same columns by their global lane).
+	// On by default with the shadow part on the full trace grid: C2 61.6 -> 58.4 ms per frame, the closest part
+	// alone on half the wave slots for 0.1 instead of 5.9 ms per frame (profiles/c2_shadow_overlap.md; a smaller
+	// shadow grid or a larger k_nee share measured slower, the closest part on 4096 equal within the spread).
+	// YAFARAY_AMD_OVERLAP_SHADOW=0 keeps the shadow part behind the join; _SHADOW_GRID is its grid (a multiple of
+	// n_seg, at most trace_grid).
+	bool ov_shadow = true;
+	int ov_shadow_grid = d.trace_grid;
+	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_SHADOW"); e && *e) ov_shadow = *e != '0';
+	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_SHADOW_GRID"); e && atoi(e) > 0)
+		ov_shadow_grid = (int)S.n_seg * std::max(1, std::min(atoi(e), d.trace_grid) / (int)S.n_seg);
+	ov_shadow = ov_shadow && overlap && d.spill.p == nullptr;
 	// The megakernel (k_path, kernels.hip; opt-in YAFARAY_AMD_PATH=mega) for scenes whose BVH, stack
 	// and tables live in LDS and need none of the wavefront-only stages (EXT shading, transparent
 	// shadows, photon maps, AO): one lane per sample, the same functions in the same order, the film
@@ -2369,7 +2390,8 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		// a light-pick count run (S.lpc_mode 1) follows the paths only: no estimates, no shadow rays
 		const bool count_run = S.lpc_mode == 1;
 		// the overlapped schedule: this iteration's closest rays were traced on the side stream beside the
-		// previous iteration's k_nee, and the render stream has waited for them
+		// previous iteration's k_nee; the render stream has waited for them (ev_join), or — with the early shadow
+		// part — waits right after this iteration's shadow launch
 		bool closest_done = false;
 		for(int it = 0; it < iters; ++it)
 		{
@@ -2381,6 +2403,8 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 			qc.tmin_dflt = it == 0 ? 0.f : S.ray_min_dist;
 			qc.perm = nullptr;
 			qc.trace_part = closest_done ? TRACE_SHADOW : TRACE_BOTH;
+			// the side stream's closest part is still running: the shadow part goes beside it, then the join
+			const bool join_pending = closest_done && ov_shadow;
 			closest_done = false;
 			if(ray_bin && it >= 1 && !count_run)
 			{
@@ -2390,8 +2414,24 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 				                        (uint32_t *)d.bin_iota.p, (uint32_t *)d.bin_perm.p, d.bin_tmp.p, &tb, d.stream));
 				qc.perm = (const uint32_t *)d.bin_perm.p;
 			}
-			PROF(KK_TRACE, yafamd_launch_trace(&S, &qc, &cnt[cur], &d.P[cur], run_stats, d.lds_stack, (int *)d.spill.p,
-			                                    S.tr_shad ? d.trace_grid_bvh4 : d.trace_grid, d.stream));
+			if(join_pending)
+			{
+				// (eligible renders only: no ray binning above, no k_tshadow / k_surface below, no spill column)
+				bool ok = [&]() -> bool {
+					PROF(KK_TRACE, yafamd_launch_trace(&S, &qc, &cnt[cur], &d.P[cur], run_stats + d.trace_grid, d.lds_stack, nullptr, ov_shadow_grid,
+					                                    d.stream));
+					HIPCHECK(hipStreamWaitEvent(d.stream, d.ev_join, 0));
+					return true;
+				}();
+				if(!ok)
+				{
+					(void)hipStreamSynchronize(d.side);   // a failed launch: leave no side-stream work behind
+					return false;
+				}
+			}
+			else
+				PROF(KK_TRACE, yafamd_launch_trace(&S, &qc, &cnt[cur], &d.P[cur], run_stats, d.lds_stack, (int *)d.spill.p,
+				                                    S.tr_shad ? d.trace_grid_bvh4 : d.trace_grid, d.stream));
 			// material-shade dispatch for textured / smooth scenes: surface attributes + shader nodes
 			// of every hit, before k_shade reads them
 			// transparent shadows: filter colours of the transparent surfaces the shadow rays crossed
@@ -2447,7 +2487,10 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 					// k_shade(it) is queued: the next iteration's closest rays go to the side stream, k_nee(it)
 					// beside them to the render stream, which then waits for the side stream — so nothing of
 					// the side stream is pending when this iteration's launches end (chunk buffers, the next
-					// pass and the render's final synchronisation see one stream, as before)
+					// pass and the render's final synchronisation see one stream, as before).  With the early shadow
+					// part that wait moves behind the next iteration's shadow launch: this branch is only taken
+					// with a next iteration, whose k_trace launch is unconditional, so the join still happens
+					// inside iterate(), ahead of that iteration's k_shade
 					DevQueues qn = d.Q[cur ^ 1];
 					qn.ray_tt = nullptr;
 					qn.tmin_dflt = S.ray_min_dist;
@@ -2462,7 +2505,8 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 						                                              ov_trace_grid, d.side));
 						HIPCHECK(hipEventRecord(d.ev_join, d.side));
 						PROF(KK_NEE, yafamd_launch_nee(&S, &d.N, &d.P[cur ^ 1], &qnee, &cnt[cur ^ 1], nee_trace_stack, d.stream));
-						HIPCHECK(hipStreamWaitEvent(d.stream, d.ev_join, 0));
+						// (the early shadow part: the next iteration joins, after its shadow launch)
+						if(!ov_shadow) HIPCHECK(hipStreamWaitEvent(d.stream, d.ev_join, 0));
 						return true;
 					}();
 					if(!ok)
@@ -2944,7 +2988,7 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 	HIPCHECK(hipEventElapsedTime(&ms, d.ev_pool[0], d.ev_pool[1]));
 	DevStats hs{};
 	{
-		std::vector<DevStats> per_block((size_t)d.trace_grid);
+		std::vector<DevStats> per_block(2 * (size_t)d.trace_grid);   // both ranges (the early shadow parts' is the second)
 		HIPCHECK(hipMemcpy(per_block.data(), d.stats.p, sizeof(DevStats) * per_block.size(), hipMemcpyDeviceToHost));
 		for(const DevStats &b : per_block)
 		{
