@@ -75,6 +75,21 @@ constexpr bool kShadeFused = false;
 #define YAF_FUSE_LEAN 0
 #endif
 constexpr int kShadeBlock = 256;
+// The camera-stage k_shade (SG_CAMERA below) has its own workgroup size: the grid stays one workgroup per
+// segment, so more resident waves per SIMD take a larger workgroup (-DYAF_SHADE_CAMERA_BLOCK=n for sweeps,
+// a multiple of 64).  Measured on C2: 256 threads (85 VGPRs, 4 waves per SIMD) 57.7-58.0 ms per
+// frame, 320 (5 waves) 58.9-59.1, 384 (6 waves, 80 VGPRs + 32 B of scratch) 58.5-58.7; 512 needs 64 B of scratch
+#ifndef YAF_SHADE_CAMERA_BLOCK
+#define YAF_SHADE_CAMERA_BLOCK 256
+#endif
+constexpr int kShadeCameraBlock = YAF_SHADE_CAMERA_BLOCK;
+
+// Compile-time stage of a k_shade launch (lean, non-fused, non-deferred instantiations only).  With compact
+// records and one path per sample the stage of every live entry follows from the iteration: iteration 0 holds
+// camera entries only (nothing else writes queue 0), iteration 1 first segments only (a diffuse camera hit
+// always starts subpath 0 with a ray, every other camera entry is finalised at once), later iterations bounce
+// and no-ray entries only.  SG_ANY is the kernel that reads the stage from the record.
+enum : int { SG_ANY = 0, SG_CAMERA = 1, SG_FIRST = 2, SG_BOUNCE = 3 };
 
 enum : uint32_t
 {
@@ -291,6 +306,12 @@ __device__ uint32_t g_nee_pm_err = 0;
 #else
 #define NEE_PM_GUARD(cond) do {} while(0)
 #endif
+// The stage-specialised k_shade launches (SG_FIRST, SG_BOUNCE) count here, per iteration (the last word takes
+// every later one), the live entries whose stage or pending flags are not those their iteration implies;
+// nothing is written on the good path.  The host reads the words after the render (yafamd_shade_stage_errors)
+// and fails it when one is set.  (SG_CAMERA reads no stage: it derives its whole record from the queue address.)
+constexpr int kStageErrWords = 32;
+__device__ uint32_t g_shade_stage_err[kStageErrWords] = {};
 __device__ __forceinline__ void neePmStore(const DevScene &S, uint4 *pm, uint32_t j, uint32_t offset, uint32_t sample_idx, uint32_t mode_l)
 {
 	if(neePm8(S))
@@ -505,7 +526,7 @@ __device__ __forceinline__ void cameraRay(const DevScene &S, const SampleCoord &
 }
 
 __global__ void __launch_bounds__(256) k_camera(DevScene S, DevPaths P, DevQueues Q, DevCounters cnt,
-                                                 const DevJob *jobs, int n_jobs, uint64_t chunk_base, int n)
+                                                 const DevJob *jobs, int n_jobs, uint64_t chunk_base, int n, int write_pr)
 {
 	// sample i of the chunk -> segment (i / 256) % n_seg, groups of 256 dense within the segment (r05: dealing
 	// the groups in eight contiguous runs, one per XCD's segments, was measured 18 % / 50 % slower on C2 / C4 —
@@ -531,7 +552,11 @@ __global__ void __launch_bounds__(256) k_camera(DevScene S, DevPaths P, DevQueue
 	// its stage — k_shade does not read them — so they are not written: 32 B per sample each way)
 	storeQRay(Q, a, from, dir);
 	if(S.cam.ray_tt) Q.ray_tt[a] = make_float2(tmin, tmax);
-	if(!S.tree) reinterpret_cast<uint2 *>(P.pr)[a] = make_uint2((uint32_t)i, ST_CAMERA);   // (RR: rrRandom)
+	if(!S.tree)
+	{
+		// (RR: rrRandom); the camera-stage k_shade reads no record (it inverts the dealing above): write_pr == 0
+		if(write_pr) reinterpret_cast<uint2 *>(P.pr)[a] = make_uint2((uint32_t)i, ST_CAMERA);
+	}
 	else
 	{
 		const int cx = sc.x + S.crop_x0, cy = sc.y + S.crop_y0;
@@ -2789,7 +2814,19 @@ struct ShadeArgs
 	const DevJob *jobs;
 	int n_jobs;
 	uint64_t chunk_base;
+	int stage_it;        // the iteration of a stage-specialised launch (g_shade_stage_err's word)
 };
+
+// The stage of a loaded record as a stage-specialised kernel sees it: a constant (camera, first) or one of two
+// values (bounce), so every test of it folds and the other stages' branches, loads and registers disappear
+template<int STAGE>
+__device__ __forceinline__ uint32_t stageOf(uint32_t stage)
+{
+	if constexpr(STAGE == SG_CAMERA) return ST_CAMERA;
+	else if constexpr(STAGE == SG_FIRST) return ST_FIRST;
+	else if constexpr(STAGE == SG_BOUNCE) return (stage & 0xffu) == ST_NORAY ? ST_NORAY : ST_BOUNCE;
+	else return stage & 0xffu;
+}
 
 __device__ __forceinline__ void writeSampleAt(const ShadeArgs &A, const SampleCoord &sc, C3 col, float alpha)
 {
@@ -2884,9 +2921,16 @@ __device__ void spawnSpecular(const DevScene &S, const DevMaterial &m, const Sur
 // every addition to the path colour (the pending light estimate with its throughput and emission, or a term known
 // at once) is written as a record chained per sample instead of being added; k_dfr_* pick the lights once the
 // pass's counter bases are known, estimate them, and fold the records in order (the same additions)
-template<bool SMALL, bool EXT, bool FUSED = false, bool LEAN = false, bool DEFER = false>
-__global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_SHADE_LEAN_WAVES : YAF_SHADE_MIN_WAVES)) k_shade(ShadeArgs A)
+// STAGE (lean, non-fused, non-deferred only; yafamd_launch_shade's hint): the launch's iteration fixes the stage of
+// every live entry (SG_* above), so the kernel carries that stage's branch alone.  SG_CAMERA also reads no record
+// (the sample id is the inverse of k_camera's dealing) and runs kShadeCameraBlock threads per segment; SG_FIRST
+// and SG_BOUNCE count the entries that contradict them in g_shade_stage_err.
+template<bool SMALL, bool EXT, bool FUSED = false, bool LEAN = false, bool DEFER = false, int STAGE = SG_ANY>
+__global__ void __launch_bounds__(STAGE == SG_CAMERA ? kShadeCameraBlock : kShadeBlock,
+                                  STAGE == SG_CAMERA ? kShadeCameraBlock / 64 : (EXT ? 1 : (LEAN ? YAF_SHADE_LEAN_WAVES : YAF_SHADE_MIN_WAVES)))
+k_shade(ShadeArgs A)
 {
+	static_assert(STAGE == SG_ANY || (LEAN && !EXT && !FUSED && !DEFER), "a fixed stage is the lean non-fused kernel's");
 	extern __shared__ uint4 shade_smem[];
 	DevScene S_ = stageTables<SMALL>(A.S, shade_smem);
 	if constexpr(LEAN)
@@ -2938,7 +2982,7 @@ __global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_SHADE_LEAN_
 	// the next iteration's compact record (the head of the entry's dependent load chain) is loaded while
 	// this one is shaded
 	uint2 pr_n = make_uint2(0u, ST_NORAY);
-	if(compact && threadIdx.x < n_a) pr_n = reinterpret_cast<const uint2 *>(Pc.pr)[a0 + threadIdx.x];
+	if(STAGE != SG_CAMERA && compact && threadIdx.x < n_a) pr_n = reinterpret_cast<const uint2 *>(Pc.pr)[a0 + threadIdx.x];
 #endif
 	for(uint32_t base_j = 0; base_j < n_a; base_j += stride)
 	{
@@ -2946,7 +2990,7 @@ __global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_SHADE_LEAN_
 		const uint32_t i = a0 + base_j + threadIdx.x;   // address of the entry (shard base + position)
 #if YAF_SHADE_PREFETCH
 		const uint2 pr_cur = pr_n;
-		if(compact && base_j + stride + threadIdx.x < n_a) pr_n = reinterpret_cast<const uint2 *>(Pc.pr)[i + stride];
+		if(STAGE != SG_CAMERA && compact && base_j + stride + threadIdx.x < n_a) pr_n = reinterpret_cast<const uint2 *>(Pc.pr)[i + stride];
 #endif
 		// ---- 0. load the entry (coalesced loads; stage, flags and w ride in the .w lanes) ----
 		uint32_t sid = 0, stage = ST_NORAY, flags = 0;
@@ -2962,12 +3006,21 @@ __global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_SHADE_LEAN_
 			{
 				// compact record: (sample id, stage), 8 B — the RR draw is a hash (rrRandom)
 #if YAF_SHADE_PREFETCH
-				const uint2 pr = pr_cur;
+				uint2 pr = pr_cur;
 #else
-				const uint2 pr = reinterpret_cast<const uint2 *>(Pc.pr)[i];
+				uint2 pr = make_uint2(0u, ST_CAMERA);
+				if(STAGE != SG_CAMERA) pr = reinterpret_cast<const uint2 *>(Pc.pr)[i];
 #endif
+				if constexpr(STAGE == SG_CAMERA)
+				{
+					// k_camera dealt sample id s to segment (s / 256) % n_seg, group (s / 256) / n_seg, lane s % 256
+					const uint32_t off = i - a0;
+					pr = make_uint2(((off / 256u) * S.n_seg + seg) * 256u + off % 256u, ST_CAMERA);
+				}
 				sid = pr.x;
 				stage = pr.y;
+				if constexpr(STAGE == SG_FIRST || STAGE == SG_BOUNCE)
+					if(stageOf<STAGE>(stage) != (stage & 0xffu)) atomicAdd(&g_shade_stage_err[min(A.stage_it, kStageErrWords - 1)], 1u);
 				sc = sampleAt(S, A.jobs, A.n_jobs, A.chunk_base + (uint64_t)sid);
 				pix = make_uint2(fnv32((uint32_t)(sc.y + S.crop_y0) * fnv32((uint32_t)(sc.x + S.crop_x0))),
 				                 S.base_offset + S.pass_offset + (uint32_t)sc.s);
@@ -2983,7 +3036,7 @@ __global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_SHADE_LEAN_
 			}
 			// a compact camera entry starts from zero throughput, colour, w and flags (k_camera does not
 			// write them) and has no first-hit data yet
-			if(!compact || (stage & 0xffu) != ST_CAMERA)
+			if(!compact || stageOf<STAGE>(stage) != ST_CAMERA)
 			{
 				if(S.w_live) thr4 = Pc.thr[i];
 				else
@@ -2998,9 +3051,20 @@ __global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_SHADE_LEAN_
 			}
 			w = thr4.w;
 			flags = __float_as_uint(pcol4.w);
+			// the pending estimate of a first segment is the camera hit's, that of a later vertex one light's
+			if constexpr(STAGE == SG_FIRST)
+			{
+				if(flags & F_PEND_ONE) atomicAdd(&g_shade_stage_err[min(A.stage_it, kStageErrWords - 1)], 1u);
+				flags &= ~F_PEND_ONE;
+			}
+			if constexpr(STAGE == SG_BOUNCE)
+			{
+				if(flags & F_PEND_V0) atomicAdd(&g_shade_stage_err[min(A.stage_it, kStageErrWords - 1)], 1u);
+				flags &= ~F_PEND_V0;
+			}
 			// only the first segment of a subpath reads the previous wo (path_tracer.cc:193-197), and only
 			// when its sample() drew nothing: a sampled segment overwrites it before any use
-			if((stage & 0xffu) == ST_FIRST && !(flags & F_SAMPLED)) pwo4 = Pc.pwo[i];
+			if(stageOf<STAGE>(stage) == ST_FIRST && !(flags & F_SAMPLED)) pwo4 = Pc.pwo[i];
 			if(flags & F_PEND_ONE)
 			{
 				const F3 t = reinterpret_cast<const F3 *>(Pc.pend_thr)[i];
@@ -3011,7 +3075,7 @@ __global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_SHADE_LEAN_
 		C3 thr = rgb(thr4), col = rgb(col4), pcol = rgb(pcol4);
 		const float alpha = 1.f;   // live entries are opaque (transparent background is written at ST_CAMERA)
 		V3 pwo = xyz(pwo4);
-		const uint32_t st = stage & 0xffu;
+		const uint32_t st = stageOf<STAGE>(stage);
 		uint32_t subpath = (stage >> 8) & 0xfffu;
 		int depth = (int)(stage >> 20);
 		const uint32_t offset = pix.x, sample_idx = pix.y;
@@ -3312,6 +3376,8 @@ __global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_SHADE_LEAN_
 			if(is_path && (flags & F_V0_DIFFUSE) && subpath + 1 < n_paths) { start_sub = true; ++subpath; }
 			else finalize = true;
 		}
+		// (one path per sample: only a camera hit starts a subpath)
+		if constexpr(STAGE == SG_FIRST || STAGE == SG_BOUNCE) start_sub = false;
 		if(live && start_sub)
 		{
 			// path_tracer.cc:168-191: first segment of subpath `subpath` from v0
@@ -3410,7 +3476,8 @@ __global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_SHADE_LEAN_
 			if(S.w_live) stStore(&Pn.thr[k], f4(thr, w));
 			else stStoreF3(Pn.thr, k, thr);
 			stStore(&Pn.pcol[k], f4(pcol, __uint_as_float(flags)));
-			if((stage & 0xffu) == ST_FIRST && !(flags & F_SAMPLED)) Pn.pwo[k] = f4(pwo, 0.f);   // (the flags just stored gate the load)
+			// (the flags just stored gate the load; of the fixed stages only the camera kernel queues first segments)
+			if((STAGE == SG_ANY || STAGE == SG_CAMERA) && (stage & 0xffu) == ST_FIRST && !(flags & F_SAMPLED)) Pn.pwo[k] = f4(pwo, 0.f);
 			if(nee_one) reinterpret_cast<F3 *>(Pn.pend_thr)[k] = F3{pend_thr.r, pend_thr.g, pend_thr.b};
 			if(flags & (F_PEND_EMIT | F_AO_EMIT)) Pn.pend_emit[k] = f4(emit_pend, 0.f);
 			if(keep_v0) { Pn.v0p[k] = v0p4; Pn.v0wo[k] = v0wo4; }
@@ -7141,6 +7208,34 @@ int yafamd_shade_fused_for(const DevScene *S)
 	        S->n_photons == 0 && !S->tree && !S->has_attr && !S->no_lean && !S->tr_shad && !S->has_mesh_light) ? 1 : 0;
 }
 
+// The scene's k_shade is the lean non-fused kernel (yafamd_launch_shade's choice below) over compact records
+// without a recursion tree: its launches may be stage-specialised (SG_*) while S->lpc_mode == 0
+int yafamd_shade_stages_for(const DevScene *S)
+{
+	return (!S->ext && !kShadeFused && S->integrator == INT_PATH && S->path_samples <= 1 && !S->do_ao && !S->caus_map && !S->gather_on && !S->show_map &&
+	        S->n_photons == 0 && !S->tree && !S->has_attr && !S->no_lean && !yafamd_shade_fused_for(S)) ? 1 : 0;
+}
+
+// The stage guard's words (g_shade_stage_err), read and cleared: the entries that iteration k's stage-specialised
+// k_shade found in another stage (the last word: every later iteration)
+int yafamd_shade_stage_errors(uint32_t *out, int n)
+{
+	uint32_t h[kStageErrWords];
+	if(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_shade_stage_err), sizeof(h)) != hipSuccess) return 0;
+	bool any = false;
+	for(int k = 0; k < kStageErrWords; ++k)
+	{
+		if(k < n) out[k] = h[k];
+		any = any || h[k] != 0u;
+	}
+	if(any)
+	{
+		const uint32_t z[kStageErrWords] = {};
+		if(hipMemcpyToSymbol(HIP_SYMBOL(g_shade_stage_err), z, sizeof(z)) != hipSuccess) return 0;
+	}
+	return kStageErrWords;
+}
+
 // Whether the measured-and-dropped pipelines are compiled in (-DYAF_EXPERIMENTS)
 int yafamd_experiments() { return kExperiments ? 1 : 0; }
 
@@ -7212,11 +7307,13 @@ int yafamd_shade_blocks_per_cu()
 }
 
 hipError_t yafamd_launch_camera(const DevScene *S, const DevPaths *P, const DevQueues *Q, const DevCounters *cnt,
-                                const DevJob *jobs, int n_jobs, uint64_t chunk_base, int n, hipStream_t st)
+                                const DevJob *jobs, int n_jobs, uint64_t chunk_base, int n, int write_pr, hipStream_t st)
 {
+	// write_pr 0: iteration 0 of this render launches the camera-stage k_shade (yafamd_launch_shade with stage_it 0),
+	// which reads no pr record
 	if(n <= 0) return hipSuccess;
 	const int threads = max(n, (int)S->n_seg);   // the first n_seg threads also write the segment counts
-	hipLaunchKernelGGL(k_camera, dim3((threads + 255) / 256), dim3(256), 0, st, *S, *P, *Q, *cnt, jobs, n_jobs, chunk_base, n);
+	hipLaunchKernelGGL(k_camera, dim3((threads + 255) / 256), dim3(256), 0, st, *S, *P, *Q, *cnt, jobs, n_jobs, chunk_base, n, write_pr);
 	return hipGetLastError();
 }
 
@@ -7305,9 +7402,13 @@ hipError_t yafamd_launch_trace(const DevScene *S, const DevQueues *Q, const DevC
 hipError_t yafamd_launch_shade(const DevScene *S, const DevPaths *Pc, const DevPaths *Pn, const DevQueues *Q,
                                const DevQueues *Qn, const DevNeeQueue *N, const DevNeeQueue *G, const DevCounters *cnt,
                                const DevCounters *cnt_next, float4 *samples, const DevJob *jobs, int n_jobs, uint64_t chunk_base,
-                               hipStream_t st)
+                               int stage_it, hipStream_t st)
 {
+	// stage_it >= 0: iteration stage_it of a render whose launches are stage-specialised (yafamd_shade_stages_for
+	// scenes; k_camera wrote no pr record); -1: the kernel that reads the stage from the record
+	if(stage_it >= 0 && !(yafamd_shade_stages_for(S) && S->cur_level == 0 && S->lpc_mode == 0)) return hipErrorInvalidValue;
 	ShadeArgs A;
+	A.stage_it = max(stage_it, 0);
 	A.S = *S;
 	A.Pc = *Pc;
 	A.Pn = *Pn;
@@ -7346,6 +7447,18 @@ hipError_t yafamd_launch_shade(const DevScene *S, const DevPaths *Pc, const DevP
 		{
 			if(S->small_tables) hipLaunchKernelGGL((k_shade<true, false, true, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
 			else hipLaunchKernelGGL((k_shade<false, false, true, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
+		}
+		else if(stage_it >= 0)
+		{
+#define YAF_SHADE_STAGE_LAUNCH(SM) \
+			do { \
+				if(stage_it == 0) hipLaunchKernelGGL((k_shade<SM, false, false, true, false, SG_CAMERA>), dim3(S->n_seg), dim3(kShadeCameraBlock), lds, st, A); \
+				else if(stage_it == 1) hipLaunchKernelGGL((k_shade<SM, false, false, true, false, SG_FIRST>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A); \
+				else hipLaunchKernelGGL((k_shade<SM, false, false, true, false, SG_BOUNCE>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A); \
+			} while(0)
+			if(S->small_tables) YAF_SHADE_STAGE_LAUNCH(true);
+			else YAF_SHADE_STAGE_LAUNCH(false);
+#undef YAF_SHADE_STAGE_LAUNCH
 		}
 		else if(S->small_tables) hipLaunchKernelGGL((k_shade<true, false, false, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
 		else hipLaunchKernelGGL((k_shade<false, false, false, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);

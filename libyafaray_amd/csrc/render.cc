@@ -22,7 +22,7 @@ using namespace yafamd;
 
 extern "C" {
 hipError_t yafamd_launch_camera(const DevScene *S, const DevPaths *P, const DevQueues *Q, const DevCounters *cnt,
-                                const DevJob *jobs, int n_jobs, uint64_t chunk_base, int n, hipStream_t st);
+                                const DevJob *jobs, int n_jobs, uint64_t chunk_base, int n, int write_pr, hipStream_t st);
 hipError_t yafamd_launch_surface(const DevScene *S, const DevQueues *Q, const DevCounters *cnt, hipStream_t st);
 hipError_t yafamd_launch_tshadow(const DevScene *S, const DevQueues *Q, const DevCounters *cnt, const DevPaths *P, hipStream_t st);
 hipError_t yafamd_launch_spawn(const DevScene *S, const DevPaths *P, const DevQueues *Q, const DevCounters *cnt, uint32_t s0, int n,
@@ -42,7 +42,9 @@ int yafamd_shade_blocks_per_cu();
 hipError_t yafamd_launch_shade(const DevScene *S, const DevPaths *Pc, const DevPaths *Pn, const DevQueues *Q,
                                const DevQueues *Qn, const DevNeeQueue *N, const DevNeeQueue *G, const DevCounters *cnt,
                                const DevCounters *cnt_next, float4 *samples, const DevJob *jobs, int n_jobs, uint64_t chunk_base,
-                               hipStream_t st);
+                               int stage_it, hipStream_t st);
+int yafamd_shade_stages_for(const DevScene *S);
+int yafamd_shade_stage_errors(uint32_t *out, int n);
 int yafamd_path_eligible(const DevScene *S, int stack_depth, int spill);
 int yafamd_path_blocks_per_cu(const DevScene *S, int stack_depth);
 hipError_t yafamd_launch_path(const DevScene *S, float4 *samples, const DevJob *jobs, int n_jobs, uint64_t chunk_base, uint32_t n,
@@ -2355,6 +2357,14 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 	S.fg_probe = 0;
 	if(const char *e = std::getenv("YAFARAY_AMD_FG_PROBE"); e && *e) S.fg_probe = atoi(e);   // timing attribution only
 	if(const char *e = std::getenv("YAFARAY_AMD_SHADE_LEAN"); e && *e == '0') S.no_lean = 1;   // tests: the general k_shade
+	// Stage-specialised k_shade launches (kernels.hip SG_*): where the scene's k_shade is the lean
+	// non-fused kernel, with one path per sample, no recursion tree and no one-thread light pick (S.lpc_mode stays
+	// 0), the stage of every live entry follows from the iteration, so iteration 0 launches the camera kernel (no
+	// pr record: k_camera writes none then), iteration 1 the first-segment kernel and the later ones the bounce
+	// kernel.  Decided once per render, for k_camera and every k_shade alike; YAFARAY_AMD_SHADE_STAGES=0 keeps the
+	// kernel that reads the stage from the record (tests, A/B).
+	bool shade_stages = !lpc_on && yafamd_shade_stages_for(&S) != 0;
+	if(const char *e = std::getenv("YAFARAY_AMD_SHADE_STAGES"); e && *e == '0') shade_stages = false;
 	int path_grid = 0;
 	if(!lpc_on)
 	{
@@ -2385,7 +2395,8 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 	// one pass: `n_total` camera samples (the jobs' enumeration, or S.plist x S.spp) through the wavefront
 	// one wavefront pass over the active list started by k_camera / k_spawn
 	DevStats *run_stats = dstats;   // the light-pick count runs count into their own statistics
-	auto iterate = [&](uint64_t base) -> bool {
+	bool shade_staged = false;      // some k_shade launch was stage-specialised: its guard words are read after the render
+	auto iterate =[&](uint64_t base) -> bool {
 		int cur = 0;
 		// a light-pick count run (S.lpc_mode 1) follows the paths only: no estimates, no shadow rays
 		const bool count_run = S.lpc_mode == 1;
@@ -2441,8 +2452,15 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 			if(S.lpc_mode == 3)
 				HIPCHECK(yafamd_dfr_segoff(&cnt[cur], S.n_seg, (uint32_t *)d.dfr_segoff.p, (uint32_t *)d.dfr_misc.p, S.dfr_cap,
 				                           (uint32_t *)d.dfr_misc.p + 1, (uint32_t *)d.dfr_its.p, d.stream));
+			// (shade_stages implies no recursion tree, so S.cur_level == 0, and no light-pick run, so S.lpc_mode == 0)
+			const int stage_it = (shade_stages && S.cur_level == 0 && S.lpc_mode == 0 && !S.tree) ? it : -1;
 			PROF(KK_SHADE, yafamd_launch_shade(&S, &d.P[cur], &d.P[cur ^ 1], &qc, &d.Q[cur ^ 1], &d.N, &d.G, &cnt[cur], &cnt[cur ^ 1],
-			                             (float4 *)d.samples.p, (const DevJob *)d.jobs.p, n_jobs, base, d.stream));
+			                             (float4 *)d.samples.p, (const DevJob *)d.jobs.p, n_jobs, base, stage_it, d.stream));
+			if(stage_it >= 0)
+			{
+				shade_staged = true;
+				if(rp.profile) ++ktimes_.launches[KK_SHADE_STAGED];
+			}
 
 			// photon-map estimates of the finished diffuse first hits: the direct-lighting pipeline
 			// (photon mapping, DirectLight) connects its NEE in iteration 1 and finishes there; path
@@ -2549,7 +2567,7 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		}
 		if(S.tree) HIPCHECK(hipMemsetAsync(d.spawn_count.p, 0, 16, d.stream));
 		S.cur_level = 0;
-		PROF(KK_CAMERA, yafamd_launch_camera(&S, &d.P[0], &d.Q[0], &cnt[0], (const DevJob *)d.jobs.p, n_jobs, base, n, d.stream));
+		PROF(KK_CAMERA, yafamd_launch_camera(&S, &d.P[0], &d.Q[0], &cnt[0], (const DevJob *)d.jobs.p, n_jobs, base, n, shade_stages ? 0 : 1, d.stream));
 		if(!iterate(base)) return false;
 		if(!S.tree) continue;
 		// recursiveRaytrace levels: the nodes the last pass spawned are the next pass's active list
@@ -2986,6 +3004,24 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 	HIPCHECK(hipStreamSynchronize(d.stream));
 	float ms = 0.f;
 	HIPCHECK(hipEventElapsedTime(&ms, d.ev_pool[0], d.ev_pool[1]));
+	if(shade_staged)
+	{
+		// the stage guard (kernels.hip g_shade_stage_err): an entry in a stage its iteration does not imply
+		uint32_t err[32] = {};
+		const int n_err = yafamd_shade_stage_errors(err, 32);
+		if(n_err <= 0)
+		{
+			log_.error("Integrator: the stage guard of k_shade could not be read");
+			return false;
+		}
+		for(int k = 0; k < n_err && k < 32; ++k)
+			if(err[k])
+			{
+				log_.error("Integrator: k_shade iteration " + std::to_string(k) + (k == n_err - 1 ? " or later" : "") + " met " + std::to_string(err[k]) +
+				           " entries of another stage than its stage-specialised kernel handles (YAFARAY_AMD_SHADE_STAGES=0 renders without them)");
+				return false;
+			}
+	}
 	DevStats hs{};
 	{
 		std::vector<DevStats> per_block(2 * (size_t)d.trace_grid);   // both ranges (the early shadow parts' is the second)
