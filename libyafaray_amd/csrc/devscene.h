@@ -43,7 +43,9 @@ enum : uint32_t { MAT_SHINYDIFFUSE = 0, MAT_LIGHT = 1, MAT_MIRROR = 2, MAT_NULL 
 // ShinyDiffuseMaterial components and options (material_shiny_diffuse.cc:38-87, 548-566)
 enum : uint32_t { SD_MIRROR = 1u, SD_TRANSPARENT = 2u, SD_TRANSLUCENT = 4u, SD_DIFFUSE = 8u, SD_FRESNEL = 16u, SD_TBIAS_MULT = 32u,
                   SD_OREN_NAYAR = 64u };
-enum : uint32_t { LIGHT_POINT = 0, LIGHT_AREA = 1, LIGHT_MESH = 2 };
+// LIGHT_SPOT and above: the types of lights_ext.h (their DevLight fields are listed there); a scene that holds
+// one sets DevScene::has_ext_light and runs the XL instantiations of k_nee, k_dfr_nee and k_photon_emit
+enum : uint32_t { LIGHT_POINT = 0, LIGHT_AREA = 1, LIGHT_MESH = 2, LIGHT_SPOT = 3, LIGHT_DIRECTIONAL = 4, LIGHT_SUN = 5, LIGHT_SPHERE = 6 };
 constexpr int kMeshTriF4 = 7;   // float4 per meshlight face (DevScene::mesh_tris)
 enum : int { INT_DIRECT = 0, INT_PATH = 1, INT_PHOTON = 2 };
 
@@ -168,7 +170,8 @@ struct DevLight
 	float du[4], dv[4];     // area: emission frame (light_area.cc:47-51), photon emission
 	float area;
 	uint32_t nee_base;      // first NEE entry of this light in the estimateAllDirectLight layout
-	uint32_t nee_count;     // point: 1, area: 2 * samples
+	uint32_t nee_count;     // point: 1, every other type: 2 * samples (light-sampled entries, then material-sampled ones;
+	                        // spot / directional: samples = 1; spot, directional and sphere never fill the second half)
 	uint32_t shoot;         // bit 0: diffuse photons, bit 1: caustic photons
 	// meshlight / objectlight (light_object_light.cc): triangles [mesh0, mesh0 + mesh_n) of
 	// DevScene::mesh_tris / mesh_cdf (the mesh's faces in creation order), double-sided emission
@@ -363,6 +366,9 @@ struct DevScene
 	int no_lean;           // 1: the general k_shade / k_nee instantiations even where a lean one applies (YAFARAY_AMD_SHADE_LEAN=0: tests, A/B)
 	int has_mesh_light;    // some light is a meshlight (k_nee's lean instantiation has no meshlight code)
 	int fg_probe;          // diagnostic (YAFARAY_AMD_FG_PROBE, wrong images): 1 = k_fg_first skips its radiance-map lookups
+	int has_ext_light;     // some light is a spot, directional, sun or sphere light (LIGHT_SPOT and above)
+	const float *spot_pdf; // the spot lights' smoothstep Pdf1D (lights_ext.h spotPdfSample): 65 function values, 65 cdf
+	                       // values, integral, 1 / integral, 1 / 65
 };
 
 struct DevFilm

@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
 #include <ctime>
 #include <random>
 #include <set>
@@ -97,6 +98,111 @@ inline float normLen(F3 &v)
 }
 inline F3 f3(const float *p) { return {p[0], p[1], p[2]}; }
 inline void put(float *dst, F3 v, float w = 0.f) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = w; }
+// Vec3::createCoordsSystem (vector.h:262-276)
+inline void coords(F3 n, F3 &u, F3 &v)
+{
+	if(n.x == 0.f && n.y == 0.f)
+	{
+		u = (n.z < 0.f) ? F3{-1.f, 0.f, 0.f} : F3{1.f, 0.f, 0.f};
+		v = {0.f, 1.f, 0.f};
+		return;
+	}
+	const float d = 1.f / std::sqrt(n.y * n.y + n.x * n.x);
+	u = {n.y * d, -n.x * d, 0.f};
+	v = crs(n, u);
+}
+// math::cos(math::degToRad(angle)) of a float angle (math.h:67-71, 243-250)
+inline float cosDeg(float angle) { return hm::cosf_fast(static_cast<float>(angle * hm::div_pi_by_180)); }
+
+// The bound Scene::getSceneBound() reports (scene.cc:1052): the kd-tree's, i.e. the union of the primitives'
+// vertex bounds, each axis widened by 0.001 of its extent (accelerator_kdtree.cc:70-85).  An instance's
+// primitives are world-space triangles here, as PrimitiveInstance::getBound's are.
+void widenBound(float *lo, float *hi)
+{
+	for(int k = 0; k < 3; ++k)
+	{
+		const double foo = (hi[k] - lo[k]) * 0.001;
+		lo[k] -= foo;
+		hi[k] += foo;
+	}
+}
+void sceneBound(const float *verts, const int *tris, int n_prims, float *lo, float *hi)
+{
+	for(int k = 0; k < 3; ++k) lo[k] = hi[k] = 0.f;
+	for(int t = 0; t < 3 * n_prims; ++t)
+	{
+		const float *v = verts + 3 * (size_t)tris[t];
+		for(int k = 0; k < 3; ++k)
+		{
+			if(t == 0 || v[k] < lo[k]) lo[k] = v[k];
+			if(t == 0 || v[k] > hi[k]) hi[k] = v[k];
+		}
+	}
+	widenBound(lo, hi);
+}
+// some light takes values from the scene bound (Light::init of the directional and sun lights)
+bool lightsNeedBound(const std::map<std::string, DevLight> &lights)
+{
+	for(const auto &kv : lights)
+		if(kv.second.type == LIGHT_DIRECTIONAL || kv.second.type == LIGHT_SUN) return true;
+	return false;
+}
+
+// Light::init of the lights that need the scene bound (light_directional.cc:42-55, light_sun.cc:45-52)
+bool initBoundLight(Logger &log, const std::string &name, DevLight &L, const HostScene &hs)
+{
+	if(L.type != LIGHT_DIRECTIONAL && L.type != LIGHT_SUN) return true;
+	if(!hs.has_bound)
+	{
+		log.error("Light '" + name + "': no scene bound");
+		return false;
+	}
+	const F3 a = f3(hs.bound_lo), g = f3(hs.bound_hi);
+	const F3 diag = sub(g, a);
+	const float world_radius = static_cast<float>(0.5 * std::sqrt(lsq(diag)));
+	const F3 centre = mul(add(a, g), 0.5f);
+	if(L.type == LIGHT_DIRECTIONAL)
+	{
+		if(L.c2[2] != 0.f)
+		{
+			put(L.pos, centre);
+			L.c2[0] = world_radius;
+		}
+		L.c2[1] = world_radius;
+		L.c2[3] = static_cast<float>(hm::num_pi * L.c2[0] * L.c2[0]);   // emitPhoton's ipdf
+		return true;
+	}
+	const float e_pdf = static_cast<float>(hm::num_pi * world_radius * world_radius);
+	put(L.c3, centre, world_radius);
+	L.c2[3] = e_pdf;
+	for(int k = 0; k < 3; ++k) L.c4[k] = L.color[k] * e_pdf;   // emitPhoton returns col_pdf * e_pdf
+	return true;
+}
+
+// The spot lights' Pdf1D over the 65 smoothstep values (light_spot.cc:45-51, sample_pdf1d.h:52-66): the
+// function, the cdf, then integral, 1 / integral and 1 / size
+std::vector<float> spotPdfTable()
+{
+	std::vector<float> t(133);
+	for(int i = 0; i < 65; i++)
+	{
+		const float v = static_cast<float>(i) / 64.f;
+		t[i] = v * v * (3.f - 2.f * v);
+	}
+	const double delta = 1.0 / 65.0;
+	double c = 0.0;
+	for(int i = 0; i < 65; ++i)
+	{
+		c += static_cast<double>(t[i]) * delta;
+		t[65 + i] = static_cast<float>(c);
+	}
+	const float integral = static_cast<float>(c);
+	for(int i = 0; i < 65; ++i) t[65 + i] /= integral;
+	t[130] = integral;
+	t[131] = 1.f / integral;
+	t[132] = 1.f / 65;
+	return t;
+}
 } // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -827,6 +933,135 @@ bool Scene::createLight(const std::string &name, const ParamMap &p)
 		L.nee_count = 2 * (uint32_t)L.samples;   // light samples + material samples (canIntersect)
 		if(enabled) light_objects[name] = object_name;
 	}
+	else if(type == "spotlight")
+	{
+		// SpotLight::factory / constructor (light_spot.cc:250-288, 30-66), the double / float mix kept
+		float from[3] = {0.f, 0.f, 0.f}, to[3] = {0.f, 0.f, -1.f};
+		float angle = 45.f, falloff = 0.15f;
+		bool soft_shadows = false;
+		p.getVec("from", from);
+		p.getVec("to", to);
+		p.get("cone_angle", angle);
+		p.get("blend", falloff);
+		p.get("soft_shadows", soft_shadows);
+		if(soft_shadows)
+		{
+			// then the light is neither Dirac nor intersectable in the reference's sense (light_spot.h:42-46)
+			log.error("Light '" + name + "': spotlight soft_shadows is not supported by the GPU core");
+			return false;
+		}
+		L.type = LIGHT_SPOT;
+		const F3 ndir = nrm(sub(f3(from), f3(to)));
+		const F3 dir = {-ndir.x, -ndir.y, -ndir.z};
+		F3 du, dv;
+		coords(dir, du, dv);
+		for(int k = 0; k < 3; ++k) { L.pos[k] = from[k]; L.color[k] = power * col[k]; }
+		put(L.fnormal, ndir);
+		put(L.to_x, dir);
+		put(L.du, du);
+		put(L.dv, dv);
+		const double rad_angle = static_cast<float>(angle * hm::div_pi_by_180);
+		const double rad_inner_angle = rad_angle * (1.f - falloff);
+		const float cos_start = hm::cosf_fast(static_cast<float>(rad_inner_angle));
+		const float cos_end = hm::cosf_fast(static_cast<float>(rad_angle));
+		L.c2[0] = cos_start;
+		L.c2[1] = cos_end;
+		L.c2[2] = 1.f / (cos_start - cos_end);
+		float interv_1 = 1.f - cos_start;
+		float interv_2 = 0.5f * (cos_start - cos_end);
+		float sum = std::abs(interv_1) + std::abs(interv_2);
+		if(sum > 0.f) sum = 1.f / sum;
+		interv_1 *= sum;
+		interv_2 *= sum;
+		L.c3[0] = interv_1;
+		L.c3[1] = interv_2;
+		L.c3[2] = static_cast<float>(hm::mult_pi_by_2 * (1.f - cos_start) / interv_1);   // emitPhoton's ipdf inside cos_start
+		L.samples = 1;
+		L.inv_samples = 1.f;
+		L.nee_count = 2;
+	}
+	else if(type == "directional")
+	{
+		// DirectionalLight::factory / constructor (light_directional.cc:116-156, 29-40); init(): initBoundLight
+		float from[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 1.f};
+		float rad = 1.f;
+		bool inf = true;
+		p.getVec("direction", dir);
+		p.get("infinite", inf);
+		if(!inf)
+		{
+			if(!p.getVec("from", from)) p.getVec("position", from);
+			p.get("radius", rad);
+		}
+		L.type = LIGHT_DIRECTIONAL;
+		const F3 direction = nrm(f3(dir));
+		F3 du, dv;
+		coords(direction, du, dv);
+		for(int k = 0; k < 3; ++k) { L.pos[k] = from[k]; L.color[k] = power * col[k]; }
+		put(L.fnormal, direction);
+		put(L.du, du);
+		put(L.dv, dv);
+		L.c2[0] = rad;
+		L.c2[2] = inf ? 1.f : 0.f;
+		L.samples = 1;
+		L.inv_samples = 1.f;
+		L.nee_count = 2;
+	}
+	else if(type == "sunlight")
+	{
+		// SunLight::factory / constructor (light_sun.cc:97-127, 29-43); init(): initBoundLight
+		float dir[3] = {0.f, 0.f, 1.f};
+		float angle = 0.27f;
+		int samples = 4;
+		p.getVec("direction", dir);
+		p.get("angle", angle);
+		p.get("samples", samples);
+		L.type = LIGHT_SUN;
+		F3 du, dv;
+		coords(f3(dir), du, dv);   // of the un-normalised direction (light_sun.cc:36)
+		put(L.fnormal, nrm(f3(dir)));
+		put(L.du, du);
+		put(L.dv, dv);
+		if(angle > 80.f) angle = 80.f;
+		const double cos_angle = cosDeg(angle);
+		const float invpdf = static_cast<float>(hm::mult_pi_by_2 * (1.f - cos_angle));
+		float pdf = static_cast<float>(1.0 / invpdf);
+		pdf = std::min(pdf, std::sqrt(std::numeric_limits<float>::max()));
+		L.c2[0] = static_cast<float>(cos_angle);
+		L.c2[1] = invpdf;
+		L.c2[2] = pdf;
+		for(int k = 0; k < 3; ++k)
+		{
+			L.to_x[k] = power * col[k];          // color_ (totalEnergy)
+			L.color[k] = pdf * L.to_x[k];        // col_pdf_
+		}
+		L.samples = std::max(1, (int)std::ceil((float)samples * 1.f));
+		L.inv_samples = 1.f / (float)L.samples;
+		L.nee_count = 2 * (uint32_t)L.samples;   // light samples + material samples (canIntersect)
+	}
+	else if(type == "spherelight")
+	{
+		// SphereLight::factory / constructor (light_sphere.cc:159-193, 31-41); object_name serves the
+		// bidirectional integrator only
+		float from[3] = {0.f, 0.f, 0.f};
+		float radius = 1.f;
+		int samples = 4;
+		p.getVec("from", from);
+		p.get("radius", radius);
+		p.get("samples", samples);
+		L.type = LIGHT_SPHERE;
+		for(int k = 0; k < 3; ++k) { L.pos[k] = from[k]; L.color[k] = power * col[k]; }
+		const float square_radius = radius * radius;
+		L.c2[0] = radius;
+		L.c2[1] = square_radius;
+		L.c2[2] = static_cast<float>(square_radius * 1.000003815);
+		L.area = static_cast<float>(square_radius * 4.0 * hm::num_pi);
+		L.samples = std::max(1, (int)std::ceil((float)samples * 1.f));
+		L.inv_samples = 1.f / (float)L.samples;
+		// the light-sampled entries, then as many that stay empty: canIntersect() is false, so
+		// areaLightSampleMaterial adds nothing (integrator_montecarlo.cc:286, 382)
+		L.nee_count = 2 * (uint32_t)L.samples;
+	}
 	else
 	{
 		log.error("Scene: light type '" + type + "' is not supported by the GPU core");
@@ -1468,6 +1703,8 @@ bool Scene::lightsAndUpload(HostScene &hs)
 				DevLight L = kv.second;
 				if((L.photon_only != 0) != (pass == 1)) continue;
 				if(L.type == LIGHT_MESH && !meshLightFaces(kv.first, L, hs)) return false;
+				if(!initBoundLight(log, kv.first, L, hs)) return false;
+				if(L.type == LIGHT_SPOT && hs.spot_pdf.empty()) hs.spot_pdf = spotPdfTable();
 				at[kv.first] = (int)hs.lights.size();
 				hs.lights.push_back(L);
 			}
@@ -1504,10 +1741,24 @@ bool Scene::buildAccelerator()
 			std::vector<float> verts;
 			std::vector<int> tris;
 			if(!gpu()->expandInstances(hs, &verts, &tris)) return false;
+			if(lightsNeedBound(lights))
+			{
+				sceneBound(verts.data(), tris.data(), hs.n_prims, hs.bound_lo, hs.bound_hi);
+				hs.has_bound = true;
+			}
 			BvhInput in{verts.data(), tris.data(), hs.n_prims};
 			if(node_cost > 0.f) in.node_cost = node_cost;
 			in.width = width;
 			hs.bvh = buildBvh(in, leaf, 8);
+		}
+		else if(lightsNeedBound(lights))
+		{
+			// the world vertices never reach the host: member 0 expands once more for the bound its expansion
+			// reduces on the device (the exact minimum and maximum over the expanded vertices)
+			if(!gpu()->expandInstances(hs)) return false;
+			gpu()->sceneBox(hs.bound_lo, hs.bound_hi);
+			widenBound(hs.bound_lo, hs.bound_hi);
+			hs.has_bound = true;
 		}
 		if(!lightsAndUpload(hs)) return false;
 		stats.build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1545,6 +1796,11 @@ bool Scene::buildAccelerator()
 	const auto t0 = std::chrono::steady_clock::now();
 	HostScene hs;
 	hs.n_prims = (int)tri_mat.size();
+	if(lightsNeedBound(lights))
+	{
+		sceneBound(verts.data(), tris.data(), hs.n_prims, hs.bound_lo, hs.bound_hi);
+		hs.has_bound = true;
+	}
 	BvhInput in{verts.data(), tris.data(), hs.n_prims};
 	int leaf = 1;   // pure SAH leaves (measured best on the Cornell box)
 	if(const char *e = getenv("YAFARAY_AMD_BVH_LEAF")) leaf = std::max(1, atoi(e));          // tuning sweeps

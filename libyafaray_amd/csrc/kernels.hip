@@ -26,6 +26,7 @@
 //
 // Compiled with -ffp-contract=off: every float expression keeps the reference's order.
 
+#include <atomic>
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <string>
@@ -2314,11 +2315,18 @@ __device__ __forceinline__ void meshSampleSurface(const DevScene &S, const DevLi
 	p = (u * v0 + v * v1) + (1.f - u - v) * v2;
 }
 
+#include "lights_ext.h"
+
 // The light-sample half of areaLightSampleLight for an area light (light_area.cc:66-96) or a mesh
 // light (light_object_light.cc:111-146): direction and distance to the sampled point and the pdf.
-template<bool NOMESH = false>
+// XL: also a sun or sphere light (lights_ext.h extIllumSample); `dist` is then the light ray's tmax (-1: no end).
+template<bool NOMESH = false, bool XL = false>
 __device__ __forceinline__ bool lightIllumSample(const DevScene &S, const DevLight &L, V3 sp_p, float s_1, float s_2, V3 &ldir, float &dist, float &pdf)
 {
+	if constexpr(XL)
+	{
+		if(L.type >= LIGHT_SPOT) return extIllumSample(L, sp_p, s_1, s_2, ldir, dist, pdf);
+	}
 	V3 p, fn;
 	if(!NOMESH && L.type == LIGHT_MESH) meshSampleSurface(S, L, s_1, s_2, p, fn);
 	else
@@ -2420,9 +2428,14 @@ __device__ int meshLightClosest(const DevScene &S, const DevLight &L, V3 o, V3 d
 // Mesh light: light_object_light.cc:183-201 — the closest face (the light's own kd-tree, faces with
 // t >= tmin) gives the normal; the reference never stores the hit distance in `t` (the caller's ray
 // tmax, -1), so 1 / (t * t) is 1 and the shadow ray is unbounded: both reproduced.
-template<bool NOMESH = false>
+// XL: also the sun (SunLight::intersect, light_sun.cc:69-77).
+template<bool NOMESH = false, bool XL = false>
 __device__ __forceinline__ bool lightMatHit(const DevScene &S, const DevLight &L, V3 p, V3 dir, float b_tmin, float &t, float &light_pdf)
 {
+	if constexpr(XL)
+	{
+		if(L.type >= LIGHT_SPOT) return sunIntersect(L, dir, t, light_pdf);
+	}
 	if(!NOMESH && L.type == LIGHT_MESH)
 	{
 		float t_best = __builtin_huge_valf();
@@ -2495,7 +2508,9 @@ __device__ __forceinline__ C3 neeGet(const NeeHbm &nee, int e)
 }
 
 // NOMESH: the scene has no meshlight (k_nee's lean instantiation drops that code)
-template<bool EXT, class Out, class NeeT, bool NOMESH = false>
+// XL: the scene has a spot, directional, sun or sphere light (DevScene::has_ext_light); every other
+// instantiation holds none of their code
+template<bool EXT, class Out, class NeeT, bool NOMESH = false, bool XL = false>
 __device__ void neeLight(const DevScene &S, const DevLight &L, const DevMaterial &m, const Surf &sp, V3 wo,
                          uint32_t loffs, uint32_t sample_idx, uint32_t offset, bool active, int e0,
                          NeeT nee, uint8_t *occ, const Out &out, float4 *ts = nullptr)
@@ -2503,6 +2518,39 @@ __device__ void neeLight(const DevScene &S, const DevLight &L, const DevMaterial
 	const bool cast_shadows = L.cast_shadows && m.receive_shadows;
 	const float p_len = length(sp.p);
 	const float sh_tmin = S.shadow_bias_auto ? S.shadow_bias * fmaxf(1.f, p_len) : S.shadow_bias;
+	if constexpr(XL)
+	{
+		if(lightIsDirac(L))
+		{
+			// spot / directional: diracLight (montecarlo.cc:80-154) with their illuminate.  They own the two entries of
+			// a one-sample light: entry 0 holds the estimate, entry 1 is never valid, and neeSumT's
+			// (0 + c * 1) + 0 is the reference's 0 + c bit for bit
+			bool ok = active;
+			C3 contrib = c3(0.f), lcol = c3(0.f);
+			V3 so = sp.p, ldir = v3(0.f, 0.f, 1.f);
+			float st = 0.f, tmax = 0.f;
+			if(ok) ok = diracIlluminate(L, sp.p, lcol, ldir, tmax);
+			if(ok)
+			{
+				const float angle = m.flat ? 1.f : fabsf(dot(sp.n, ldir));
+				const C3 surf_col = matEval<EXT>(m, sp, wo, ldir, B_ALL);
+				const C3 transmit = c3(1.f);
+				contrib = surf_col * lcol * angle * transmit;
+				shadowRayOf(sp.p, ldir, sh_tmin, tmax, so, st);
+				if(ts && cast_shadows) tsFactors(ts, e0, surf_col, angle, lcol, 1.f, 1.f, false);
+			}
+			if(active)
+			{
+				neePut(nee, occ, e0, contrib, ok);
+				neePut(nee, occ, e0 + 1, c3(0.f), false);
+			}
+			out.emit(ok && cast_shadows, so, ldir, st, sh_tmin, e0);
+			return;
+		}
+	}
+	// XL: a light that cannot be intersected (the sphere light) weighs its light samples by 1 and has no
+	// material-sampled ones (montecarlo.cc:222, 286); the sun takes both halves like an area light
+	const bool no_hit = XL && L.type == LIGHT_SPHERE;
 	if(L.type == LIGHT_POINT)
 	{
 		// light_point.cc:38-57 + montecarlo.cc:80-154
@@ -2561,7 +2609,7 @@ __device__ void neeLight(const DevScene &S, const DevLight &L, const DevMaterial
 		{
 			// light_area.cc:66-96 / light_object_light.cc:111-146
 			float dist = 0.f, pdf = 0.f;
-			ok = lightIllumSample<NOMESH>(S, L, sp.p, s_1, s_2, ldir, dist, pdf);
+			ok = lightIllumSample<NOMESH, XL>(S, L, sp.p, s_1, s_2, ldir, dist, pdf);
 			if(ok)
 			{
 				if(pdf > 1e-6f)
@@ -2569,12 +2617,15 @@ __device__ void neeLight(const DevScene &S, const DevLight &L, const DevMaterial
 					const C3 surf_col = matEval<EXT>(m, sp, wo, ldir, B_ALL);
 					const float angle = m.flat ? 1.f : fabsf(dot(sp.n, ldir));
 					float w = 1.f;
-					const float m_pdf = matPdf<EXT>(m, sp, wo, ldir, B_GLOSSY | B_DIFFUSE | B_DISPERSIVE | B_REFLECT | B_TRANSMIT);
-					if(m_pdf > 1e-6f)
+					if(!no_hit)
 					{
-						const float l_2 = pdf * pdf;
-						const float m_2 = m_pdf * m_pdf;
-						w = l_2 / (l_2 + m_2);
+						const float m_pdf = matPdf<EXT>(m, sp, wo, ldir, B_GLOSSY | B_DIFFUSE | B_DISPERSIVE | B_REFLECT | B_TRANSMIT);
+						if(m_pdf > 1e-6f)
+						{
+							const float l_2 = pdf * pdf;
+							const float m_2 = m_pdf * m_pdf;
+							w = l_2 / (l_2 + m_2);
+						}
 					}
 					contrib = surf_col * lcolor * angle * w / pdf;
 					shadowRayOf(sp.p, ldir, sh_tmin, dist, so, st);
@@ -2587,7 +2638,7 @@ __device__ void neeLight(const DevScene &S, const DevLight &L, const DevMaterial
 		out.emit(ok && cast_shadows, so, ldir, st, sh_tmin, e0 + i);
 
 		// areaLightSampleMaterial (montecarlo.cc:284-383)
-		ok = active;
+		ok = active && !no_hit;
 		contrib = c3(0.f);
 		so = sp.p;
 		V3 dir = v3(0.f, 0.f, 1.f);
@@ -2609,7 +2660,7 @@ __device__ void neeLight(const DevScene &S, const DevLight &L, const DevMaterial
 			{
 				// light_area.cc:137-151
 				// light_area.cc:137-151 / light_object_light.cc:183-201
-				ok = lightMatHit<NOMESH>(S, L, sp.p, dir, b_tmin, t, lpdf);
+				ok = lightMatHit<NOMESH, XL>(S, L, sp.p, dir, b_tmin, t, lpdf);
 			}
 			if(ok)
 			{
@@ -3926,7 +3977,7 @@ __host__ __device__ inline size_t neeTraceLdsBytes(const DevScene &S, int stack_
 #endif
 // LEAN: no ambient occlusion, transparent shadows or meshlights (launch_nee picks it), so their code and
 // registers drop out
-template<bool SMALL, bool EXT, bool TR = false, bool TSTATS = false, bool LEAN = false>
+template<bool SMALL, bool EXT, bool TR = false, bool TSTATS = false, bool LEAN = false, bool XL = false>
 __global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_NEE_LEAN_WAVES : YAF_NEE_MIN_WAVES)) k_nee(NeeArgs A)
 {
 	extern __shared__ uint4 shade_smem[];
@@ -4058,7 +4109,7 @@ __global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_NEE_LEAN_WA
 		{
 			// estimateAllDirectLight (montecarlo.cc:54-68)
 			for(int l = 0; l < S.n_lights; ++l)
-				neeLight<EXT, ShadeOut, NeeHbm, LEAN>(S, S.lights[l], S.mats[sp.mat], sp, wo, (uint32_t)l, pm.y, pm.x, all,
+				neeLight<EXT, ShadeOut, NeeHbm, LEAN, XL>(S, S.lights[l], S.mats[sp.mat], sp, wo, (uint32_t)l, pm.y, pm.x, all,
 				         e0 + (int)S.lights[l].nee_base, neeHbm(A.Pn), A.Pn.occ, out, S.tr_shad ? A.Pn.ts : nullptr);
 			if(S.do_ao)
 				aoSamples<EXT>(S, S.mats[sp.mat], sp, wo, pm.y, pm.x, all, e0 + S.nee_all_count, neeHbm(A.Pn), A.Pn.occ, out,
@@ -4071,7 +4122,7 @@ __global__ void __launch_bounds__(kShadeBlock, EXT ? 1 : (LEAN ? YAF_NEE_LEAN_WA
 			{
 				const bool mine = one && lnum == (uint32_t)l;
 				if(!__any(mine)) continue;
-				neeLight<EXT, ShadeOut, NeeHbm, LEAN>(S, S.lights[l], S.mats[sp.mat], sp, wo, (uint32_t)l, pm.y, pm.x, mine, e0, neeHbm(A.Pn), A.Pn.occ, out,
+				neeLight<EXT, ShadeOut, NeeHbm, LEAN, XL>(S, S.lights[l], S.mats[sp.mat], sp, wo, (uint32_t)l, pm.y, pm.x, mine, e0, neeHbm(A.Pn), A.Pn.occ, out,
 				              S.tr_shad ? A.Pn.ts : nullptr);
 			}
 		}
@@ -4264,7 +4315,7 @@ __global__ void __launch_bounds__(1024) k_dfr_part(DfrArgs A)
 }
 
 // LEAN: no meshlight in the scene (neeLight's NOMESH: no private arrays), k_nee's occupancy
-template<bool SMALL, bool LEAN>
+template<bool SMALL, bool LEAN, bool XL = false>
 __global__ void __launch_bounds__(kShadeBlock, LEAN ? YAF_NEE_LEAN_WAVES : YAF_NEE_MIN_WAVES) k_dfr_nee(DfrArgs A)
 {
 	extern __shared__ uint4 shade_smem[];
@@ -4310,7 +4361,7 @@ __global__ void __launch_bounds__(kShadeBlock, LEAN ? YAF_NEE_LEAN_WAVES : YAF_N
 		{
 			const bool mine = live && lnum == (uint32_t)l;
 			if(!__any(mine)) continue;
-			neeLight<false, ShadeOut, NeeHbm, LEAN>(S, S.lights[l], S.mats[sp.mat], sp, wo, (uint32_t)l, pix.y, pix.x, mine,
+			neeLight<false, ShadeOut, NeeHbm, LEAN, XL>(S, S.lights[l], S.mats[sp.mat], sp, wo, (uint32_t)l, pix.y, pix.x, mine,
 			                                  e0, neeHbm(A.P), A.P.occ, out, nullptr);
 		}
 	}
@@ -5068,6 +5119,8 @@ struct PhotonArgs
 };
 
 // :127-156 — photon id h: light pick by Pdf1D::dSample over the lights' energies, emitPhoton
+// XL: the scene has a spot, directional, sun or sphere light (lights_ext.h extEmitPhoton)
+template<bool XL>
 __global__ void __launch_bounds__(256) k_photon_emit(PhotonArgs A)
 {
 	const DevScene &S = A.S;
@@ -5098,8 +5151,10 @@ __global__ void __launch_bounds__(256) k_photon_emit(PhotonArgs A)
 		const float light_num_pdf = A.L.func[light_num] * A.L.inv_integral;
 		const DevLight &L = S.lights[A.L.lights[light_num]];
 		float light_pdf;
+		C3 ecol = C3{L.color[0], L.color[1], L.color[2]};   // emitPhoton's result
 		// light_area.cc:98-104, light_point.cc:79-85
-		if(L.type == LIGHT_POINT)
+		if(XL && L.type >= LIGHT_SPOT) ecol = extEmitPhoton(S, L, s_1, s_2, s_3, s_4, o, d, light_pdf);
+		else if(L.type == LIGHT_POINT)
 		{
 			o = lv(L.pos);
 			d = sphereDir(s_1, s_2);
@@ -5128,7 +5183,7 @@ __global__ void __launch_bounds__(256) k_photon_emit(PhotonArgs A)
 			d = cosHemisphere(-lv(L.fnormal), lv(L.du), lv(L.dv), s_1, s_2);
 		}
 		const float f_num_lights = static_cast<float>(nl);
-		pcol = C3{L.color[0], L.color[1], L.color[2]} * (f_num_lights * light_pdf / light_num_pdf);
+		pcol = ecol * (f_num_lights * light_pdf / light_num_pdf);
 		ok = !isBlack(pcol);
 	}
 	// the path's place in the alive list: position i, i.e. segment i / seg_cap (the bounce workgroup that
@@ -6427,7 +6482,8 @@ __device__ __forceinline__ int pkNearestLds(const uint4 *nodes, const float4 *di
 // shadows (tr_shad_, :112, 206, 330): the surfaces a shadow ray crosses are collected in ts_buf
 // (s_depth entries of this lane) and their filter colour scol multiplies the light colour
 // (:122, 212, 335) as k_tshadow does for the wavefront path.
-template<bool EXT, bool WIDE, bool SPILL = true, bool TSH = false>
+// XL: the scene has a spot, directional, sun or sphere light (as neeLight's XL).
+template<bool EXT, bool WIDE, bool SPILL = true, bool TSH = false, bool XL = false>
 __device__ C3 lightEstimateInline(const DevScene &S, const TraceCtx &C, const DevLight &L, const DevMaterial &m, const Surf &sp, V3 wo,
                                   uint32_t loffs, uint32_t sample_idx, uint32_t offset, uint32_t &visits, uint32_t &tests,
                                   float2 *ts_buf = nullptr)
@@ -6455,6 +6511,28 @@ __device__ C3 lightEstimateInline(const DevScene &S, const TraceCtx &C, const De
 		}
 		return traverse<true, WIDE, SPILL>(C, so, dir, 0.f, st, t_hit, p_hit, visits, tests);
 	};
+	if constexpr(XL)
+	{
+		if(lightIsDirac(L))
+		{
+			// spot / directional: diracLight with their illuminate (lights_ext.h)
+			C3 c = c3(0.f), lcol = c3(0.f);
+			V3 ldir = v3(0.f, 0.f, 1.f);
+			float tmax = 0.f;
+			if(diracIlluminate(L, sp.p, lcol, ldir, tmax))
+			{
+				const float angle = m.flat ? 1.f : fabsf(dot(sp.n, ldir));
+				const C3 surf_col = matEval<EXT>(m, sp, wo, ldir, B_ALL);
+				V3 so;
+				float st;
+				shadowRayOf(sp.p, ldir, sh_tmin, tmax, so, st);
+				C3 scol;
+				if(!shadowed(so, ldir, sh_tmin, st, scol)) c = c + surf_col * (TSH && cast_shadows ? lcol * scol : lcol) * angle * c3(1.f);
+			}
+			return c3(0.f) + c;
+		}
+	}
+	const bool no_hit = XL && L.type == LIGHT_SPHERE;   // not intersectable: w = 1, no material samples
 	if(L.type == LIGHT_POINT)
 	{
 		C3 c = c3(0.f);
@@ -6495,7 +6573,7 @@ __device__ C3 lightEstimateInline(const DevScene &S, const TraceCtx &C, const De
 		{
 			V3 ldir = v3(0.f, 0.f, 1.f);
 			float dist = 0.f, pdf = 0.f;
-			const bool ok = lightIllumSample(S, L, sp.p, s_1, s_2, ldir, dist, pdf);
+			const bool ok = lightIllumSample<false, XL>(S, L, sp.p, s_1, s_2, ldir, dist, pdf);
 			if(ok)
 			{
 				if(pdf > 1e-6f)
@@ -6503,12 +6581,15 @@ __device__ C3 lightEstimateInline(const DevScene &S, const TraceCtx &C, const De
 					const C3 surf_col = matEval<EXT>(m, sp, wo, ldir, B_ALL);
 					const float angle = m.flat ? 1.f : fabsf(dot(sp.n, ldir));
 					float w = 1.f;
-					const float m_pdf = matPdf<EXT>(m, sp, wo, ldir, B_GLOSSY | B_DIFFUSE | B_DISPERSIVE | B_REFLECT | B_TRANSMIT);
-					if(m_pdf > 1e-6f)
+					if(!no_hit)
 					{
-						const float l_2 = pdf * pdf;
-						const float m_2 = m_pdf * m_pdf;
-						w = l_2 / (l_2 + m_2);
+						const float m_pdf = matPdf<EXT>(m, sp, wo, ldir, B_GLOSSY | B_DIFFUSE | B_DISPERSIVE | B_REFLECT | B_TRANSMIT);
+						if(m_pdf > 1e-6f)
+						{
+							const float l_2 = pdf * pdf;
+							const float m_2 = m_pdf * m_pdf;
+							w = l_2 / (l_2 + m_2);
+						}
 					}
 					V3 so;
 					float st;
@@ -6520,6 +6601,7 @@ __device__ C3 lightEstimateInline(const DevScene &S, const TraceCtx &C, const De
 			}
 		}
 		// areaLightSampleMaterial (montecarlo.cc:284-383), light_area.cc:137-151
+		if(!no_hit)
 		{
 			BsdfSample s;
 			s.s_1 = s_1;
@@ -6535,7 +6617,7 @@ __device__ C3 lightEstimateInline(const DevScene &S, const TraceCtx &C, const De
 			if(ok)
 			{
 				// light_area.cc:137-151 / light_object_light.cc:183-201
-				ok = lightMatHit(S, L, sp.p, dir, b_tmin, t, lpdf);
+				ok = lightMatHit<false, XL>(S, L, sp.p, dir, b_tmin, t, lpdf);
 			}
 			if(ok)
 			{
@@ -6622,7 +6704,7 @@ __host__ __device__ inline bool fgStageTables(const DevScene &S, bool lds_scene,
 	const size_t tab_b = (size_t)S.n_mats * sizeof(DevMaterial) + (size_t)S.n_tris * 16u;
 	return stack_b + scene_b + nstk_b + tab_b <= (size_t)64 * 1024;
 }
-template<bool LDS_SCENE, bool WIDE, bool EXT, bool SPILL = true, bool TSH = false>
+template<bool LDS_SCENE, bool WIDE, bool EXT, bool SPILL = true, bool TSH = false, bool XL = false>
 __global__ void __launch_bounds__(kTraceBlock) YAF_FG_ATTR k_fg(FgArgs A)
 {
 	DevScene S_ = A.S;
@@ -6745,7 +6827,7 @@ __global__ void __launch_bounds__(kTraceBlock) YAF_FG_ATTR k_fg(FgArgs A)
 						const uint32_t lnum = pickLight(S, offset, sample_idx, (uint32_t)i * (uint32_t)max(1, S.fg_bounces) + (uint32_t)depth,
 						                                (uint32_t)n_sampl * (uint32_t)(max(1, S.fg_bounces) + 1));
 						lcol = (S.n_lights > 0)
-						           ? lightEstimateInline<EXT, WIDE, SPILL, TSH>(S, C, S.lights[lnum], mh, hit, pwo, lnum, sample_idx, offset, visits, tests,
+						           ? lightEstimateInline<EXT, WIDE, SPILL, TSH, XL>(S, C, S.lights[lnum], mh, hit, pwo, lnum, sample_idx, offset, visits, tests,
 						                                                        ts_buf) *
 						                 (float)S.n_lights
 						           : c3(0.f);
@@ -7196,6 +7278,11 @@ extern "C" {
 
 int yafamd_trace_block() { return kTraceBlock; }
 
+// Launches of an XL instantiation (k_nee, k_dfr_nee, k_photon_emit, k_fg with the spot, directional, sun and
+// sphere code) since the library was loaded: the profile mode reports the count of a render as "k_lights_xl"
+static std::atomic<unsigned long long> g_xl_launches{0};
+unsigned long long yafamd_xl_launches() { return g_xl_launches.load(); }
+
 // Whether the non-EXT k_shade runs the next-event estimation itself (then render.cc launches no
 // k_nee for those scenes); -DYAF_FUSE builds that variant (measured slower, see kShadeFused).
 int yafamd_shade_fused() { return kShadeFused ? 1 : 0; }
@@ -7205,7 +7292,7 @@ int yafamd_shade_fused_for(const DevScene *S)
 	if(S->ext) return 0;
 	if(kShadeFused) return 1;
 	return (YAF_FUSE_LEAN && S->integrator == INT_PATH && S->path_samples <= 1 && !S->do_ao && !S->caus_map && !S->gather_on && !S->show_map &&
-	        S->n_photons == 0 && !S->tree && !S->has_attr && !S->no_lean && !S->tr_shad && !S->has_mesh_light) ? 1 : 0;
+	        S->n_photons == 0 && !S->tree && !S->has_attr && !S->no_lean && !S->tr_shad && !S->has_mesh_light && !S->has_ext_light) ? 1 : 0;
 }
 
 // The scene's k_shade is the lean non-fused kernel (yafamd_launch_shade's choice below) over compact records
@@ -7501,6 +7588,13 @@ hipError_t yafamd_dfr_nee(const DevScene *S, const DevPaths *P, const DevQueues 
 	A.n_rec = n_rec;
 	hipLaunchKernelGGL(k_dfr_part, dim3(S->n_seg), dim3(1024), 0, st, A);
 	const size_t lds = shadeLdsBytes(*S, S->small_tables != 0);
+	if(S->has_ext_light)
+	{
+		++g_xl_launches;
+		if(S->small_tables) hipLaunchKernelGGL((k_dfr_nee<true, false, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
+		else hipLaunchKernelGGL((k_dfr_nee<false, false, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
+		return hipGetLastError();
+	}
 	const bool lean = !S->has_mesh_light;
 	if(S->small_tables) { if(lean) hipLaunchKernelGGL((k_dfr_nee<true, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
 	                      else hipLaunchKernelGGL((k_dfr_nee<true, false>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A); }
@@ -7564,7 +7658,7 @@ hipError_t yafamd_launch_tshadow(const DevScene *S, const DevQueues *Q, const De
 // hipErrorInvalidValue when the scene is not eligible (yafamd_path_eligible).
 int yafamd_path_eligible(const DevScene *S, int stack_depth, int spill)
 {
-	return (kExperiments && !S->ext && !S->tree && !S->tr_shad && !S->has_attr && !S->do_ao && !S->gather_on && !S->caus_map && S->integrator != INT_PHOTON &&
+	return (kExperiments && !S->has_ext_light && !S->ext && !S->tree && !S->tr_shad && !S->has_attr && !S->do_ao && !S->gather_on && !S->caus_map && S->integrator != INT_PHOTON &&
 	        S->scene_in_lds && S->node_f4 == 8 && !spill && S->small_tables && S->nee_k >= 1 && S->nee_k <= kPathMaxK && !S->brute &&
 	        pathLdsBytes(*S, stack_depth) <= 64 * 1024)
 	           ? 1
@@ -7600,7 +7694,7 @@ hipError_t yafamd_launch_path(const DevScene *S, float4 *samples, const DevJob *
 // fits LDS, without transparent shadows (their filter colours need k_tshadow's lists)
 int yafamd_nee_trace_eligible(const DevScene *S, int stack_depth)
 {
-	return (kExperiments && !S->ext && !S->tr_shad && !S->has_attr && S->scene_in_lds && S->node_f4 == 8 && S->small_tables && S->nee_k >= 1 &&
+	return (kExperiments && !S->has_ext_light && !S->ext && !S->tr_shad && !S->has_attr && S->scene_in_lds && S->node_f4 == 8 && S->small_tables && S->nee_k >= 1 &&
 	        S->nee_k <= kPathMaxK && !S->brute && neeTraceLdsBytes(*S, stack_depth) <= 64 * 1024)
 	           ? 1
 	           : 0;
@@ -7627,7 +7721,19 @@ hipError_t yafamd_launch_nee(const DevScene *S, const DevNeeQueue *N, const DevP
 		return hipGetLastError();
 	}
 #endif
-	if(S->ext)
+	if(S->has_ext_light)
+	{
+		// the general kernels with the spot, directional, sun and sphere code (XL)
+		++g_xl_launches;
+		if(S->ext)
+		{
+			if(S->small_tables) hipLaunchKernelGGL((k_nee<true, true, false, false, false, true>), dim3(grid), dim3(kShadeBlock), lds, st, A);
+			else hipLaunchKernelGGL((k_nee<false, true, false, false, false, true>), dim3(grid), dim3(kShadeBlock), lds, st, A);
+		}
+		else if(S->small_tables) hipLaunchKernelGGL((k_nee<true, false, false, false, false, true>), dim3(grid), dim3(kShadeBlock), lds, st, A);
+		else hipLaunchKernelGGL((k_nee<false, false, false, false, false, true>), dim3(grid), dim3(kShadeBlock), lds, st, A);
+	}
+	else if(S->ext)
 	{
 		if(S->small_tables) hipLaunchKernelGGL((k_nee<true, true>), dim3(grid), dim3(kShadeBlock), lds, st, A);
 		else hipLaunchKernelGGL((k_nee<false, true>), dim3(grid), dim3(kShadeBlock), lds, st, A);
@@ -7659,7 +7765,9 @@ hipError_t yafamd_photon_emit(const DevScene *S, const PhotonState *P, const Pho
 	A.stack_depth = 0;
 	A.spill = nullptr;
 	if(n_local == 0) return hipSuccess;
-	hipLaunchKernelGGL(k_photon_emit, dim3((n_local + 255) / 256), dim3(256), 0, st, A);
+	if(S->has_ext_light) ++g_xl_launches;
+	if(S->has_ext_light) hipLaunchKernelGGL(k_photon_emit<true>, dim3((n_local + 255) / 256), dim3(256), 0, st, A);
+	else hipLaunchKernelGGL(k_photon_emit<false>, dim3((n_local + 255) / 256), dim3(256), 0, st, A);
 	return hipGetLastError();
 }
 
@@ -7854,6 +7962,9 @@ hipError_t yafamd_launch_fg(const DevScene *S, const DevNeeQueue *G, const DevCo
 	const size_t stack_bytes = (size_t)stack_depth * kTraceBlock * sizeof(int);
 	const size_t nstk_bytes = (size_t)S->rpk_lds * kTraceBlock * sizeof(uint32_t);
 	const bool wide = S->node_f4 == 8;
+	// XL: the k_fg instantiations with the spot, directional, sun and sphere code (lightEstimateInline's XL)
+	const bool xl = S->has_ext_light != 0;
+	if(xl) ++g_xl_launches;
 	// an LDS-resident scene: the column rounded to 16 B, then the staged tables (fgStageTables)
 	const size_t stage_bytes = fgStageTables(*S, S->scene_in_lds != 0, S->ext != 0, stack_depth)
 	                               ? ((nstk_bytes + 15) & ~(size_t)15) + (size_t)S->n_mats * sizeof(DevMaterial) + (size_t)S->n_tris * 16
@@ -7864,7 +7975,12 @@ hipError_t yafamd_launch_fg(const DevScene *S, const DevNeeQueue *G, const DevCo
 		if(!ts_scratch) return hipErrorInvalidValue;
 		const size_t bytes = (S->scene_in_lds ? stack_bytes + (size_t)(S->node_f4 * S->n_nodes + 3 * S->n_tris) * sizeof(float4) : stack_bytes) +
 		                     (S->scene_in_lds ? stage_bytes : nstk_bytes);
-#define YAF_FG_LAUNCH_TS(L, W, E) hipLaunchKernelGGL((k_fg<L, W, E, true, true>), dim3(grid), dim3(kTraceBlock), bytes, st, A)
+#define YAF_FG_LAUNCH_TS(L, W, E)                                                                                              \
+	do                                                                                                                         \
+	{                                                                                                                          \
+		if(xl) hipLaunchKernelGGL((k_fg<L, W, E, true, true, true>), dim3(grid), dim3(kTraceBlock), bytes, st, A);            \
+		else hipLaunchKernelGGL((k_fg<L, W, E, true, true>), dim3(grid), dim3(kTraceBlock), bytes, st, A);                    \
+	} while(0)
 		if(S->scene_in_lds)
 		{
 			if(S->ext) { if(wide) YAF_FG_LAUNCH_TS(true, true, true); else YAF_FG_LAUNCH_TS(true, false, true); }
@@ -7877,8 +7993,18 @@ hipError_t yafamd_launch_fg(const DevScene *S, const DevNeeQueue *G, const DevCo
 #undef YAF_FG_LAUNCH_TS
 		return hipGetLastError();
 	}
-#define YAF_FG_LAUNCH(L, W, E, B) hipLaunchKernelGGL((k_fg<L, W, E>), dim3(grid), dim3(kTraceBlock), B, st, A)
-#define YAF_FG_LAUNCH_NS(W, E, B) hipLaunchKernelGGL((k_fg<true, W, E, false>), dim3(grid), dim3(kTraceBlock), B, st, A)
+#define YAF_FG_LAUNCH(L, W, E, B)                                                                                              \
+	do                                                                                                                         \
+	{                                                                                                                          \
+		if(xl) hipLaunchKernelGGL((k_fg<L, W, E, true, false, true>), dim3(grid), dim3(kTraceBlock), B, st, A);               \
+		else hipLaunchKernelGGL((k_fg<L, W, E>), dim3(grid), dim3(kTraceBlock), B, st, A);                                    \
+	} while(0)
+#define YAF_FG_LAUNCH_NS(W, E, B)                                                                                              \
+	do                                                                                                                         \
+	{                                                                                                                          \
+		if(xl) hipLaunchKernelGGL((k_fg<true, W, E, false, false, true>), dim3(grid), dim3(kTraceBlock), B, st, A);           \
+		else hipLaunchKernelGGL((k_fg<true, W, E, false>), dim3(grid), dim3(kTraceBlock), B, st, A);                          \
+	} while(0)
 	if(S->scene_in_lds)
 	{
 		const size_t bytes = stack_bytes + (size_t)(S->node_f4 * S->n_nodes + 3 * S->n_tris) * sizeof(float4) + stage_bytes;
@@ -7905,6 +8031,7 @@ hipError_t yafamd_launch_fg(const DevScene *S, const DevNeeQueue *G, const DevCo
 int yafamd_fg_paths_eligible(const DevScene *S)
 {
 	if(!S->scene_in_lds || S->tr_shad) return 0;
+	if(S->has_ext_light) return 0;   // k_fg_long's light estimate has no XL form: k_fg serves these scenes
 	const char *e = getenv("YAFARAY_AMD_FG");
 	return (e && std::string(e) == "lane") ? 0 : 1;
 }

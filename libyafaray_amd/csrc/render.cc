@@ -33,6 +33,7 @@ hipError_t yafamd_launch_trace(const DevScene *S, const DevQueues *Q, const DevC
                                DevStats *stats, int stack_depth, int *spill, int grid, hipStream_t st);
 int yafamd_trace_block();
 int yafamd_shade_fused();
+unsigned long long yafamd_xl_launches();
 int yafamd_walk_lds_levels(int pm_stack);
 int yafamd_walk_threads(const DevScene *S);
 int yafamd_shade_fused_for(const DevScene *S);
@@ -315,6 +316,7 @@ struct GpuRenderer::Impl
 	Buf cph_pos, cph_dir, cph_colb, cpk_nodes;   // caustic photon map + kd-tree
 	Buf tile_rank, pfilm;                        // tile order ranks; partial film of the per-tile callbacks
 	Buf mesh_tris, mesh_cdf;                     // meshlight faces and area distributions
+	Buf spot_pdf;                                // the spot lights' smoothstep Pdf1D (HostScene::spot_pdf)
 	Buf mesh_nodes, mesh_btris;                  // meshlight BVH2s (nodes, triangle records)
 	int c_photons = 0, c_paths = 0, c_depth = 0;
 	Buf ph_ray_o, ph_ray_d, ph_pcol, ph_alive0, ph_alive1, ph_n_alive, dep_a, dep_b, dep_c, dep_flag, ph_scan, ph_total;
@@ -422,7 +424,7 @@ struct GpuRenderer::Impl
 		for(Buf &b : chunk_bufs) b.release();
 		for(Buf *b : {&lay_rec, &lay_albedo, &lay_accum, &lay_film, &lay_pfilm, &lay_mat, &lay_obj, &lay_depth}) b->release();
 		for(Buf *b : {&g_send, &g_recv, &g_wsend, &g_wrecv, &g_times, &g_status}) b->release();
-		for(Buf *b : {&fg_ts, &g_log, &g_log_n, &walk_spill, &path_next, &lpc, &lpc_seg, &lpc_stats, &mesh_tris, &mesh_cdf, &mesh_nodes, &mesh_btris, &pre_stats, &fg_terms, &fg_longs,
+		for(Buf *b : {&fg_ts, &g_log, &g_log_n, &walk_spill, &path_next, &lpc, &lpc_seg, &lpc_stats, &mesh_tris, &mesh_cdf, &spot_pdf, &mesh_nodes, &mesh_btris, &pre_stats, &fg_terms, &fg_longs,
 		              &fg_long_terms, &fg_long_count, &bin_keys, &bin_keys2, &bin_iota, &bin_perm, &bin_tmp, &dfr_kind, &dfr_pp,
 		              &dfr_wo, &dfr_a, &dfr_emit, &dfr_pix, &dfr_last, &dfr_segoff, &dfr_misc, &dfr_its, &dfr_pcol,
 		              &dfr_idx, &dfr_nrec}) b->release();
@@ -618,6 +620,10 @@ bool GpuRenderer::expandInstances(const HostScene &hs, std::vector<float> *verts
 }
 
 bool GpuRenderer::hasWorldVerts() const { return d_->world_verts.p != nullptr; }
+void GpuRenderer::sceneBox(float *lo, float *hi) const
+{
+	for(int a = 0; a < 3; ++a) { lo[a] = d_->scene_lo[a]; hi[a] = d_->scene_hi[a]; }
+}
 int GpuRenderer::primitiveCount() const { return d_->n_tris; }
 
 bool GpuRenderer::readPrimitives(int first, int count, float *verts9, float *ng3, float *vnormals9, int *material)
@@ -659,6 +665,8 @@ bool GpuRenderer::readPrimitives(int first, int count, float *verts9, float *ng3
 	}
 	return true;
 }
+
+static float extLightEnergy(const DevLight &L, int k);
 
 bool GpuRenderer::upload(HostScene &hs)
 {
@@ -749,6 +757,11 @@ bool GpuRenderer::upload(HostScene &hs)
 			return false;
 	}
 	else for(Buf *b : {&d.mesh_tris, &d.mesh_cdf, &d.mesh_nodes, &d.mesh_btris}) b->release();
+	if(!hs.spot_pdf.empty())
+	{
+		if(!allocCopy(log_, d.spot_pdf, hs.spot_pdf.data(), hs.spot_pdf.size())) return false;
+	}
+	else d.spot_pdf.release();
 	d.has_attr = hs.has_attr;
 	d.n_textures = (int)hs.textures.size();
 	// the attribute rows: the scene's own (has_attr: k_surface reads them) or for the render layers only
@@ -785,10 +798,13 @@ bool GpuRenderer::upload(HostScene &hs)
 				const DevLight &L = hs.lights[i];
 				if(!(L.shoot & (1u << set))) continue;
 				float e[3];
-				// point: 4 pi color; area: color * area; mesh (light_object_light.cc:109): double-sided ? 2 color area : color area
+				// point: 4 pi color; area: color * area; mesh (light_object_light.cc:109): double-sided ? 2 color area : color area;
+				// spot (light_spot.cc:70): color * 2 pi * (1 - 0.5 (cos_start + cos_end)); directional (light_directional.h):
+				// color * radius^2 * pi; sun (light_sun.h): color * e_pdf; sphere (light_sphere.cc:53): color * area
 				for(int k = 0; k < 3; ++k)
 					e[k] = (L.type == LIGHT_POINT)   ? static_cast<float>(3.14159265358979323846264338327950288L) * (4.0f * L.color[k])
 					       : (L.type == LIGHT_MESH) ? (L.double_sided ? (2.f * L.color[k]) * L.area : L.color[k] * L.area)
+					       : (L.type >= LIGHT_SPOT) ? extLightEnergy(L, k)
 					                                : L.area * L.color[k];
 				func.push_back((e[0] + e[1] + e[2]) * 0.333333f);
 				idx.push_back(i);
@@ -922,6 +938,21 @@ bool GpuRenderer::upload(HostScene &hs)
 	return true;
 }
 
+// totalEnergy() of a spot, directional, sun or sphere light, channel k (light_spot.cc:68-71, light_directional.h:42,
+// light_sun.h:42, light_sphere.cc:53; the long double constants act as floats: Rgb * float)
+static float extLightEnergy(const DevLight &L, int k)
+{
+	const float pi_f = static_cast<float>(3.14159265358979323846264338327950288L);
+	const float two_pi_f = static_cast<float>(6.283185307179586476925286766559L);
+	switch(L.type)
+	{
+		case LIGHT_SPOT: return (L.color[k] * two_pi_f) * (1.f - 0.5f * (L.c2[0] + L.c2[1]));
+		case LIGHT_DIRECTIONAL: return ((L.color[k] * L.c2[0]) * L.c2[0]) * pi_f;
+		case LIGHT_SUN: return L.to_x[k] * L.c2[3];   // to_x: color * power (color holds col_pdf)
+		default: return L.color[k] * L.area;
+	}
+}
+
 static void fillScenePointers(GpuRenderer::Impl &d, DevScene &S)
 {
 	S.nodes = (const float4 *)d.nodes.p;
@@ -934,6 +965,9 @@ static void fillScenePointers(GpuRenderer::Impl &d, DevScene &S)
 	S.lights = (const DevLight *)d.lights.p;
 	S.has_mesh_light = 0;
 	for(const DevLight &L : d.host_lights) S.has_mesh_light |= L.type == LIGHT_MESH ? 1 : 0;
+	S.has_ext_light = 0;
+	for(const DevLight &L : d.host_lights) S.has_ext_light |= L.type >= LIGHT_SPOT ? 1 : 0;
+	S.spot_pdf = (const float *)d.spot_pdf.p;
 	S.mesh_tris = (const float4 *)d.mesh_tris.p;
 	S.mesh_nodes = (const float4 *)d.mesh_nodes.p;
 	S.mesh_btris = (const float4 *)d.mesh_btris.p;
@@ -1844,12 +1878,22 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 	d.ev_n = 2;
 	d.prof_recs.clear();
 	ktimes_ = KernelTimes{};
+	const unsigned long long xl0 = yafamd_xl_launches();
 	S.caus_map = 0;
 	S.gather_on = 0;
 	S.n_photons = 0;
 	S.fg_on = 0;
 	S.n_rphotons = 0;
 	S.rpk_lds = 0;
+	if(S.has_ext_light)
+	{
+		// the fused tuning k_shade samples the lights itself and has none of the spot, directional, sun and sphere code
+		if(yafamd_shade_fused())
+		{
+			log_.error("Integrator: this tuning build (fused k_shade) has no spot, directional, sun or sphere lights");
+			return false;
+		}
+	}
 	if(S.integrator == INT_PHOTON || rp.pm.caustic_map)
 	{
 		// PhotonIntegrator::preprocess (integrator_photon_mapping.cc:242-638) / createCausticMap
@@ -2075,7 +2119,7 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		for(DevLight &L : ls)
 		{
 			if(L.photon_only) continue;   // no NEE entries (after the visible lights)
-			if(L.type == LIGHT_AREA || L.type == LIGHT_MESH)
+			if(L.type == LIGHT_AREA || L.type == LIGHT_MESH || L.type == LIGHT_SUN || L.type == LIGHT_SPHERE)
 			{
 				L.samples = (int)ceilf((float)L.samples * mult);
 				L.inv_samples = 1.f / (float)L.samples;
@@ -3079,6 +3123,7 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		ktimes_.items[KK_PATH] = ktimes_.launches[KK_PATH] ? samples_total : 0;
 		ktimes_.items[KK_SHADE] = hs.shade_entries;
 		ktimes_.items[KK_NEE] = hs.nee_requests;
+		ktimes_.launches[KK_LIGHTS_XL] = yafamd_xl_launches() - xl0;
 		ktimes_.items[KK_GATHER] = hs.gather_queries;
 		ktimes_.items[KK_GATHER_WALK] = ktimes_.launches[KK_GATHER_WALK] ? hs.gather_queries : 0;
 		ktimes_.items[KK_FG] = S.fg_on ? hs.gather_queries : 0;   // every diffuse-map request runs its final gathering first

@@ -38,6 +38,10 @@ struct HostScene
 	std::vector<float> mesh_cdf;         // their area distributions' normalised cdf, per light
 	std::vector<float> mesh_nodes;       // each meshlight's BVH2 over its faces (16 floats per node)
 	std::vector<float> mesh_btris;       // ... and its triangle records in leaf order (12 floats each)
+	std::vector<float> spot_pdf;         // spot lights: their smoothstep Pdf1D (DevScene::spot_pdf), empty without one
+	// the scene bound as the reference's Scene::getSceneBound() reports it (directional and sun lights: Light::init)
+	bool has_bound = false;
+	float bound_lo[3] = {0.f, 0.f, 0.f}, bound_hi[3] = {0.f, 0.f, 0.f};
 	int n_prims = 0;
 	// A scene with object instances (Scene::addInstance): verts / tris / prim_ng / prim_attr hold the
 	// SOURCE rows — every visible plain mesh and every instanced base once, in object space, tris local
@@ -102,6 +106,7 @@ enum KernelKind : int
 	KK_PHOTON_EMIT, KK_PHOTON_BOUNCE, KK_PHOTON_COMPACT, KK_PHOTON_TREE, KK_FG, KK_PREGATHER, KK_GATHER_WALK, KK_PATH, KK_DFR,
 	KK_LAYER_HITS, KK_LAYER_FILM,
 	KK_SHADE_STAGED,   // launches only: the k_shade launches (counted and timed under KK_SHADE) that were stage-specialised
+	KK_LIGHTS_XL,      // launches only: the k_nee / k_dfr / k_photon_emit / k_fg launches that ran an XL instantiation (lights_ext.h)
 	KK_COUNT
 };
 inline const char *kernelKindName(int k)
@@ -109,7 +114,7 @@ inline const char *kernelKindName(int k)
 	static const char *n[KK_COUNT] = {"k_camera", "k_trace", "k_surface", "k_tshadow", "k_shade", "k_nee", "k_gather", "k_spawn",
 	                                  "k_combine", "k_film", "aa_next_pass", "k_photon_emit", "k_photon_bounce", "photon_compact",
 	                                  "pkd_build", "k_fg", "k_pregather", "k_gather_walk", "k_path", "k_dfr", "k_layer_hits", "k_layer_film",
-	                                  "k_shade_staged"};
+	                                  "k_shade_staged", "k_lights_xl"};
 	return (k >= 0 && k < KK_COUNT) ? n[k] : "";
 }
 struct KernelTimes
@@ -222,6 +227,7 @@ class GpuRenderer
 		// instanced scenes only (a plain scene's vertices are the host objects' own); null = skipped
 		bool readPrimitives(int first, int count, float *verts9, float *ng3, float *vnormals9, int *material);
 		bool hasWorldVerts() const;
+		void sceneBox(float *lo, float *hi) const;   // the expanded vertices' bound of the last expandInstances
 		int primitiveCount() const;
 		bool render(RenderParams &rp, volatile bool *canceled);
 		int lastPassCount() const { return passes_done_; }

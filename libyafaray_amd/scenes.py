@@ -76,7 +76,7 @@ class TextureSpec:
 @dataclass
 class Light:
     name: str
-    type: str = "pointlight"               # or "arealight"
+    type: str = "pointlight"               # arealight meshlight objectlight spotlight directional sunlight spherelight
     color: tuple = (1.0, 1.0, 1.0)
     power: float = 1.0
     from_: tuple = (0.0, 0.0, 0.0)         # pointlight
@@ -90,6 +90,15 @@ class Light:
     object_name: str = ""                  # meshlight / objectlight: the emitting object
     double_sided: bool = False             # meshlight
     photon_only: bool = False              # shoots photons only (Light::photonOnly, render_view.cc:83-111)
+    # spotlight (from_, to, cone_angle, blend), directional (direction, infinite; from_ and radius when
+    # not infinite), sunlight (direction, angle, samples), spherelight (from_, radius, samples)
+    to: tuple = (0.0, 0.0, -1.0)
+    cone_angle: float = 45.0
+    blend: float = 0.15
+    direction: tuple = (0.0, 0.0, 1.0)
+    infinite: bool = True
+    radius: float = 1.0
+    angle: float = 0.27
 
 
 @dataclass
@@ -568,6 +577,25 @@ def apply(spec: SceneSpec, api) -> None:
         elif l.type in ("meshlight", "objectlight"):
             api.paramsSetString("object_name", l.object_name)
             api.paramsSetBool("double_sided", l.double_sided)
+            api.paramsSetInt("samples", l.samples)
+        elif l.type == "spotlight":
+            api.paramsSetVector("from", *l.from_)
+            api.paramsSetVector("to", *l.to)
+            api.paramsSetFloat("cone_angle", l.cone_angle)
+            api.paramsSetFloat("blend", l.blend)
+        elif l.type == "directional":
+            api.paramsSetVector("direction", *l.direction)
+            api.paramsSetBool("infinite", l.infinite)
+            if not l.infinite:
+                api.paramsSetVector("from", *l.from_)
+                api.paramsSetFloat("radius", l.radius)
+        elif l.type == "sunlight":
+            api.paramsSetVector("direction", *l.direction)
+            api.paramsSetFloat("angle", l.angle)
+            api.paramsSetInt("samples", l.samples)
+        elif l.type == "spherelight":
+            api.paramsSetVector("from", *l.from_)
+            api.paramsSetFloat("radius", l.radius)
             api.paramsSetInt("samples", l.samples)
         else:
             api.paramsSetVector("corner", *l.corner)
