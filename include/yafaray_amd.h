@@ -93,6 +93,20 @@ YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_buildAccelerator(yafaray_Interfa
 YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_traceClosest(yafaray_Interface_t *interface, const float *rays, int n, float *t, int *prims);
 YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_traceShadow(yafaray_Interface_t *interface, const float *rays, int n, int *occluded);
 
+/* Test infrastructure (LIBYAFARAY_AMD_1.9): the same queries through the kernel a render of this scene launches
+ * (k_trace with its queues, per-segment counters, LDS stack levels, spill column and statistics), where
+ * traceClosest / traceShadow run a plain traversal of their own.  The rays are dealt over n_seg queue segments
+ * (1 <= n_seg <= the trace grid) with ragged counts; part: 0 both ray kinds, 1 closest only, 2 shadow only (the
+ * launches of the overlapped schedule; the refill loops of scenes in global memory take 0 only).  A closest
+ * ray whose direction x is NaN is the queue's "no ray" entry.  t, prims and occluded are in / out: entries
+ * the kernel does not write keep the caller's values; a miss gets the kernel's own (prim -1, t = the ray's
+ * tmax or infinity).  counted[0], counted[1]: the closest and shadow rays the launch's statistics report.
+ * Statistics on / off follow yafaray_amd_setTraceStats.  False (and a logged error) for a scene without
+ * accelerator, n_seg outside its range or a part the scene's kernel does not take. */
+YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_traceQueued(yafaray_Interface_t *interface, const float *closest_rays, int n_closest,
+                                                            const float *shadow_rays, int n_shadow, int n_seg, int part, float *t, int *prims,
+                                                            int *occluded, unsigned long long *counted);
+
 /* The built scene's primitives [first, first + count) in creation order (instances expanded, as the
  * ray queries number them), as the device holds them: verts9 the three world-space vertices, ng3 the
  * geometric normal, vnormals9 the three vertex normals (the geometric normal where the primitive is

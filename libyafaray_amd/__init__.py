@@ -138,6 +138,8 @@ def lib():
             "yafaray_amd_buildAccelerator": (b, [vp]),
             "yafaray_amd_traceClosest": (b, [vp, C.POINTER(C.c_float), i, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
             "yafaray_amd_traceShadow": (b, [vp, C.POINTER(C.c_float), i, C.POINTER(C.c_int)]),
+            "yafaray_amd_traceQueued": (b, [vp, C.POINTER(C.c_float), i, C.POINTER(C.c_float), i, i, i, C.POINTER(C.c_float),
+                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]),
             "yafaray_amd_getFilm": (b, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
             "yafaray_amd_getFilmDevice": (b, [vp, vp, i, i]),
             "yafaray_amd_getLayerCount": (i, [vp]),
@@ -434,6 +436,34 @@ class Interface:
                                               o.ctypes.data_as(C.POINTER(C.c_int))):
             raise RuntimeError("traceShadow failed: " + self.last_error())
         return o
+
+    TRACE_PARTS = {"both": 0, "closest": 1, "shadow": 2}
+
+    def trace_queued(self, closest_rays, shadow_rays, n_seg=None, part="both", sentinel_t=-7.0, sentinel_prim=-7,
+                     sentinel_occ=-7):
+        """Test infrastructure (yafaray_amd_traceQueued): the rays through the k_trace launch a render of this
+        scene uses, dealt over n_seg ragged queue segments (None: the render's own segment count).  Returns
+        (t, prim, occluded, closest_counted, shadow_counted); entries the kernel did not write hold the
+        sentinels."""
+        fp = C.POINTER(C.c_float)
+        cr = np.ascontiguousarray(closest_rays, np.float32).reshape(-1)
+        sr = np.ascontiguousarray(shadow_rays, np.float32).reshape(-1)
+        nc, ns = len(cr) // 8, len(sr) // 8
+        if n_seg is None:
+            if self.L.yafaray_amd_traceQueued(self.h, None, 0, None, 0, 1, 0, None, None, None, None):   # (builds the accelerator)
+                n_seg = int(self.stats()["shade_grid"])
+            else:
+                raise RuntimeError("traceQueued failed: " + self.last_error())
+        t = np.full(max(nc, 1), sentinel_t, np.float32)
+        p = np.full(max(nc, 1), sentinel_prim, np.int32)
+        o = np.full(max(ns, 1), sentinel_occ, np.int32)
+        counted = (C.c_ulonglong * 2)()
+        if not self.L.yafaray_amd_traceQueued(self.h, cr.ctypes.data_as(fp), nc, sr.ctypes.data_as(fp), ns, int(n_seg),
+                                              self.TRACE_PARTS[part], t.ctypes.data_as(fp), p.ctypes.data_as(C.POINTER(C.c_int)),
+                                              o.ctypes.data_as(C.POINTER(C.c_int)), counted):
+            raise RuntimeError("traceQueued failed: " + self.last_error())
+        return t[:nc], p[:nc], o[:ns], int(counted[0]), int(counted[1])
+
 
 
 def render_group_id() -> bytes:

@@ -499,6 +499,29 @@ yafaray_bool_t yafaray_amd_traceShadow(yafaray_Interface_t *interface, const flo
 	return YAFARAY_BOOL_TRUE;
 }
 
+yafaray_bool_t yafaray_amd_traceQueued(yafaray_Interface_t *interface, const float *closest_rays, int n_closest, const float *shadow_rays,
+                                       int n_shadow, int n_seg, int part, float *t, int *prims, int *occluded, unsigned long long *counted)
+{
+	Scene *s = I(interface)->sc();
+	if(!s) return YAFARAY_BOOL_FALSE;
+	if(s->geometry_dirty && !s->buildAccelerator()) return YAFARAY_BOOL_FALSE;
+	uint64_t c[2] = {0, 0};
+	if(!s->gpu()->traceRaysQueued(closest_rays, n_closest, shadow_rays, n_shadow, n_seg, part, s->trace_stats, t, prims, occluded, c))
+		return YAFARAY_BOOL_FALSE;
+	if(counted) { counted[0] = c[0]; counted[1] = c[1]; }
+	// what the launch traversed, readable through getStats without a render (the counters of the last render stay)
+	const yafaray_amd_stats_t &g = s->gpu()->stats();
+	s->stats.bvh_nodes = g.bvh_nodes;
+	s->stats.bvh_depth = g.bvh_depth;
+	s->stats.bvh_width = g.bvh_width;
+	s->stats.scene_in_lds = g.scene_in_lds;
+	s->stats.trace_grid = g.trace_grid;
+	s->stats.shade_grid = g.shade_grid;
+	s->stats.trace_block = g.trace_block;
+	s->stats.stack_depth = g.stack_depth;
+	return YAFARAY_BOOL_TRUE;
+}
+
 yafaray_bool_t yafaray_amd_getFilm(const yafaray_Interface_t *interface, float *rgba, float *weights)
 {
 	const Interface *it = I(interface);

@@ -3265,6 +3265,171 @@ bool GpuRenderer::traceRays(bool any, const float *rays, int n, float *t, int *p
 	return ok;
 }
 
+// Test infrastructure (yafaray_amd_traceQueued): n rays dealt over n_seg queue segments with ragged counts.
+// Segment s takes kRagged[(s + phase) % 6] rays while rays remain (empty segments, counts of 1, 63, 64, 65 and
+// 257: below, at and above a wave, and above a workgroup); what is left after one round is spread evenly over
+// the segments of a non-zero share, so empty segments stay empty.  One segment takes everything.
+static std::vector<uint32_t> dealRagged(uint32_t n, uint32_t n_seg, uint32_t phase)
+{
+	static const uint32_t kRagged[6] = {0u, 1u, 63u, 64u, 65u, 257u};
+	std::vector<uint32_t> count(n_seg, 0u);
+	if(n_seg == 1) { count[0] = n; return count; }
+	uint32_t left = n, takers = 0;
+	for(uint32_t s = 0; s < n_seg; ++s)
+	{
+		const uint32_t share = kRagged[(s + phase) % 6];
+		takers += share ? 1u : 0u;
+		count[s] = std::min(share, left);
+		left -= count[s];
+	}
+	for(uint32_t s = 0, k = 0; s < n_seg && left > 0; ++s)
+	{
+		if(!kRagged[(s + phase) % 6]) continue;
+		const uint32_t extra = (left + (takers - k) - 1) / (takers - k);   // ceil over the takers still to come
+		count[s] += extra;
+		left -= extra;
+		++k;
+	}
+	return count;
+}
+
+// The production k_trace launch on caller-supplied rays: the queues, counters and launch parameters are those
+// iterate() hands yafamd_launch_trace (closest rays as 12-B records with an optional (tmin, tmax) side array,
+// shadow rays prepared by Accelerator::isShadowed's rule with their own index in sh_o.w, per-segment counts,
+// the render's LDS stack levels, spill column and a grid that is a multiple of n_seg within trace_grid), so the
+// kernel variant is the one a render of this scene launches.  t / prim / occluded come in pre-filled by the
+// caller: entries the kernel does not write (no-ray entries, the ray kind a partial launch leaves out) keep
+// their values.  counted[0 .. 1] = the closest / shadow rays the launch's own statistics records report.
+bool GpuRenderer::traceRaysQueued(const float *closest, int n_closest, const float *shadow, int n_shadow, int n_seg, int part,
+                                  bool trace_stats, float *t, int *prim, int *occluded, uint64_t *counted)
+{
+	if(!ready()) return false;
+	DeviceGuard guard(device_);
+	Impl &d = *d_;
+	if(!d.nodes.p || d.n_tris <= 0) { log_.error("GPU: traceQueued: no acceleration structure built"); return false; }
+	if(n_closest < 0 || n_shadow < 0 || (n_closest && (!closest || !t || !prim)) || (n_shadow && (!shadow || !occluded)))
+	{
+		log_.error("GPU: traceQueued: bad ray arrays");
+		return false;
+	}
+	if(n_seg <= 0 || n_seg > d.trace_grid) { log_.error("GPU: traceQueued: n_seg must lie in [1, trace_grid]"); return false; }
+	if(part != TRACE_BOTH && part != TRACE_CLOSEST && part != TRACE_SHADOW) { log_.error("GPU: traceQueued: bad part"); return false; }
+	const int grid = n_seg * (d.trace_grid / n_seg);
+	if(grid <= 0) { log_.error("GPU: traceQueued: empty grid"); return false; }
+	// (only k_trace's plain loop reads trace_part: LDS-resident scenes and the BVH2 in global memory)
+	const bool refill = !d.scene_in_lds && (d.node_f4 == 8 || d.nodes8.p);
+	if(part != TRACE_BOTH && refill) { log_.error("GPU: traceQueued: the refill loops trace both ray kinds in one launch"); return false; }
+	if(d.lds_stack < d.stack_depth && !d.spill.p) { log_.error("GPU: traceQueued: no spill column"); return false; }
+
+	const std::vector<uint32_t> na = dealRagged((uint32_t)n_closest, (uint32_t)n_seg, 0u);
+	const std::vector<uint32_t> ns = dealRagged((uint32_t)n_shadow, (uint32_t)n_seg, 3u);
+	const uint32_t cap_a = std::max(1u, *std::max_element(na.begin(), na.end()));
+	const uint32_t cap_s = std::max(1u, *std::max_element(ns.begin(), ns.end()));
+	if((uint64_t)cap_a * (uint64_t)n_seg >= (1ull << 28) || (uint64_t)cap_s * (uint64_t)n_seg >= (1ull << 28))
+	{
+		log_.error("GPU: traceQueued: too many rays for this n_seg");
+		return false;
+	}
+	const size_t NA = (size_t)cap_a * n_seg, NS = (size_t)cap_s * n_seg;
+
+	// closest queue: ray i of segment s sits at s * cap_a + j; (tmin, tmax) ride in ray_tt unless every ray
+	// has the first one's tmin and no bound (a bounce queue: tmin_dflt)
+	std::vector<float> ro(3 * NA, 0.f), rd(3 * NA, 0.f), ht(NA, 0.f);
+	std::vector<float2> tt(NA, make_float2(0.f, -1.f));
+	std::vector<int> hp(NA, 0);
+	std::vector<uint32_t> qa((size_t)n_closest);
+	bool need_tt = false;
+	{
+		uint32_t i = 0;
+		for(int s = 0; s < n_seg; ++s)
+			for(uint32_t j = 0; j < na[s]; ++j, ++i)
+			{
+				const size_t q = (size_t)s * cap_a + j;
+				const float *r = closest + 8 * (size_t)i;
+				for(int k = 0; k < 3; ++k) { ro[3 * q + k] = r[k]; rd[3 * q + k] = r[3 + k]; }
+				tt[q] = make_float2(r[6], r[7]);
+				ht[q] = t[i];
+				hp[q] = prim[i];
+				qa[i] = (uint32_t)q;
+				const bool no_ray = r[3] != r[3];
+				if(!no_ray && (r[7] >= 0.f || std::memcmp(&r[6], &closest[6], sizeof(float)) != 0)) need_tt = true;
+			}
+	}
+	// shadow queue: Accelerator::isShadowed (accelerator.cc:69-78, kernels.hip shadowRayOf) — the origin moves by
+	// tmin, t_max = tmax - 2 tmin or infinite; the ray's own index is its occlusion slot
+	std::vector<float4> so(NS, make_float4(0.f, 0.f, 0.f, 0.f)), sd(NS, make_float4(0.f, 0.f, 1.f, 0.f));
+	{
+		uint32_t i = 0;
+		for(int s = 0; s < n_seg; ++s)
+			for(uint32_t j = 0; j < ns[s]; ++j, ++i)
+			{
+				const size_t q = (size_t)s * cap_s + j;
+				const float *r = shadow + 8 * (size_t)i;
+				const float tmin = r[6], tmax = r[7];
+				float idx_bits;
+				const uint32_t idx = i;
+				std::memcpy(&idx_bits, &idx, sizeof(float));
+				so[q] = make_float4(r[0] + r[3] * tmin, r[1] + r[4] * tmin, r[2] + r[5] * tmin, idx_bits);
+				sd[q] = make_float4(r[3], r[4], r[5], (tmax >= 0.f) ? tmax - 2 * tmin : std::numeric_limits<float>::infinity());
+			}
+	}
+	constexpr uint8_t kOccUntouched = 0xEE;
+	std::vector<uint8_t> occ((size_t)std::max(n_shadow, 1), kOccUntouched);
+
+	Buf b_ro, b_rd, b_tt, b_ht, b_hp, b_so, b_sd, b_occ, b_na, b_ns, b_stats;
+	bool ok = allocCopy(log_, b_ro, ro.data(), ro.size()) && allocCopy(log_, b_rd, rd.data(), rd.size()) &&
+	          allocCopy(log_, b_tt, tt.data(), tt.size()) && allocCopy(log_, b_ht, ht.data(), ht.size()) &&
+	          allocCopy(log_, b_hp, hp.data(), hp.size()) && allocCopy(log_, b_so, so.data(), so.size()) &&
+	          allocCopy(log_, b_sd, sd.data(), sd.size()) && allocCopy(log_, b_occ, occ.data(), occ.size()) &&
+	          allocCopy(log_, b_na, na.data(), na.size()) && allocCopy(log_, b_ns, ns.data(), ns.size()) &&
+	          ensure(log_, b_stats, sizeof(DevStats) * (size_t)grid);
+	std::vector<DevStats> per_block((size_t)grid);
+	if(ok)
+	{
+		DevScene S{};
+		fillScenePointers(d, S);
+		S.n_seg = (uint32_t)n_seg;
+		S.cap_a = cap_a;
+		S.cap_s = cap_s;
+		S.trace_stats = trace_stats ? 1 : 0;
+		S.tr_shad = 0;
+		DevQueues Q{};
+		Q.ray_o = (float *)b_ro.p;
+		Q.ray_d = (float *)b_rd.p;
+		Q.ray_tt = need_tt ? (float2 *)b_tt.p : nullptr;
+		Q.tmin_dflt = n_closest ? closest[6] : 0.f;
+		Q.hit_t = (float *)b_ht.p;
+		Q.hit_prim = (int *)b_hp.p;
+		Q.sh_o = (float4 *)b_so.p;
+		Q.sh_d = (float4 *)b_sd.p;
+		Q.perm = nullptr;
+		Q.trace_part = part;
+		DevCounters cnt{};
+		cnt.n_active = (uint32_t *)b_na.p;
+		cnt.n_shadow = (uint32_t *)b_ns.p;
+		DevPaths P{};
+		P.occ = (uint8_t *)b_occ.p;
+		ok = hipMemsetAsync(b_stats.p, 0, sizeof(DevStats) * (size_t)grid, d.stream) == hipSuccess &&
+		     yafamd_launch_trace(&S, &Q, &cnt, &P, (DevStats *)b_stats.p, d.lds_stack, (int *)d.spill.p, grid, d.stream) == hipSuccess &&
+		     hipStreamSynchronize(d.stream) == hipSuccess;
+		if(!ok) log_.error("GPU: traceQueued: launch failed");
+		ok = ok && hipMemcpy(ht.data(), b_ht.p, NA * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess &&
+		     hipMemcpy(hp.data(), b_hp.p, NA * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess &&
+		     hipMemcpy(occ.data(), b_occ.p, occ.size(), hipMemcpyDeviceToHost) == hipSuccess &&
+		     hipMemcpy(per_block.data(), b_stats.p, sizeof(DevStats) * (size_t)grid, hipMemcpyDeviceToHost) == hipSuccess;
+	}
+	for(Buf *b : {&b_ro, &b_rd, &b_tt, &b_ht, &b_hp, &b_so, &b_sd, &b_occ, &b_na, &b_ns, &b_stats}) b->release();
+	if(!ok) return false;
+	for(int i = 0; i < n_closest; ++i) { t[i] = ht[qa[i]]; prim[i] = hp[qa[i]]; }
+	for(int i = 0; i < n_shadow; ++i) if(occ[i] != kOccUntouched) occluded[i] = occ[i];
+	if(counted)
+	{
+		counted[0] = counted[1] = 0;
+		for(const DevStats &b : per_block) { counted[0] += b.closest_rays; counted[1] += b.shadow_rays; }
+	}
+	return true;
+}
+
 // ---------------------------------------------------------------------------------------------
 // render group
 // ---------------------------------------------------------------------------------------------

@@ -240,6 +240,9 @@ class GpuRenderer
 		int layerCount() const;
 		bool downloadLayers(std::vector<float> &rgba, bool accum);
 		bool traceRays(bool any, const float *rays, int n, float *t, int *prim);
+		// test infrastructure: the rays through the production k_trace launch (queues of n_seg ragged segments; part = TRACE_*)
+		bool traceRaysQueued(const float *closest, int n_closest, const float *shadow, int n_shadow, int n_seg, int part,
+		                     bool trace_stats, float *t, int *prim, int *occluded, uint64_t *counted);
 		bool buildPhotonMap(RenderParams &rp);
 		bool buildRadianceMap(RenderParams &rp);
 		bool shootMap(RenderParams &rp, const PhotonSet &L, uint32_t N, int bounces, int which, uint32_t &n_out, int &depth_out);

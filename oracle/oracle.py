@@ -669,18 +669,32 @@ class OracleScene:
         oracle_lib().yc_render_samples(C.byref(self.sc), C.c_int(n), _p(xys, C.c_int), _p(out, C.c_float))
         return out.reshape(n, 4)
 
-    def trace_closest(self, rays):
+    def trace_closest(self, rays, exhaustive=False):
+        """Closest hits: (t, barycentrics) and primitive per ray.  exhaustive=True loops over every
+        triangle instead of walking the oracle's own BVH (no box test: for rays on which culling
+        itself is in question)."""
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1)
         n = len(rays) // 8
         hit = np.empty(4 * n, np.float32)
         prim = np.empty(n, np.int32)
-        oracle_lib().yc_trace_closest(C.byref(self.sc), C.c_int(n), _p(rays, C.c_float), _p(hit, C.c_float),
-                                      _p(prim, C.c_int))
+        fn = oracle_lib().yc_trace_closest_exhaustive if exhaustive else oracle_lib().yc_trace_closest
+        fn(C.byref(self.sc), C.c_int(n), _p(rays, C.c_float), _p(hit, C.c_float), _p(prim, C.c_int))
         return hit.reshape(n, 4), prim
 
-    def trace_shadow(self, rays):
+    def trace_shadow(self, rays, exhaustive=False):
+        """Any hit with 0 <= t < tmax from the ray's origin as given (Accelerator::intersectS; isShadowed's
+        origin shift is the caller's)."""
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1)
         n = len(rays) // 8
         occ = np.empty(n, np.int32)
-        oracle_lib().yc_trace_shadow(C.byref(self.sc), C.c_int(n), _p(rays, C.c_float), _p(occ, C.c_int))
+        fn = oracle_lib().yc_trace_shadow_exhaustive if exhaustive else oracle_lib().yc_trace_shadow
+        fn(C.byref(self.sc), C.c_int(n), _p(rays, C.c_float), _p(occ, C.c_int))
         return occ
+
+    def trace_ties(self, rays):
+        """Per ray the number of primitives that hit at exactly the closest t (0: miss, >= 2: an exact tie)."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1)
+        n = len(rays) // 8
+        cnt = np.empty(n, np.int32)
+        oracle_lib().yc_trace_ties(C.byref(self.sc), C.c_int(n), _p(rays, C.c_float), _p(cnt, C.c_int))
+        return cnt

@@ -3515,6 +3515,95 @@ int yc_trace_shadow(const yc_scene *s, int n, const float *rays, int *occluded)
 	return 0;
 }
 
+// The same two queries without any culling: every triangle is tested with triIntersect, the closest
+// hit is the lowest (t, primitive) with tmin <= t < t_max, a shadow ray is occluded by any hit with
+// 0 <= t < t_max.  No box, no traversal order: the statement every accelerator claims to equal
+// (accelerator_simple_test.cc:61-139), for rays on which a conservative box test is itself in question.
+int yc_trace_closest_exhaustive(const yc_scene *s, int n, const float *rays, float *hit, int *prim)
+{
+	Scene sc(*s);
+	const int n_tris = (int)sc.tris.size();
+	for(int k = 0; k < n; ++k)
+	{
+		const float *r = rays + 8 * k;
+		Ray ray;
+		ray.from = V3(r[0], r[1], r[2]);
+		ray.dir = V3(r[3], r[4], r[5]);
+		ray.tmin = r[6];
+		ray.tmax = r[7];
+		const float t_max = (ray.tmax >= 0.f) ? ray.tmax : std::numeric_limits<float>::infinity();
+		IsectData best;
+		for(int pi = 0; pi < n_tris; ++pi)
+		{
+			IsectData d = triIntersect(sc.tris[pi], ray);
+			if(!d.hit || !(d.t >= ray.tmin && d.t < t_max)) continue;
+			// ascending primitive order: a strictly lower t replaces, an equal one keeps the lower index
+			if(best.hit && !(d.t < best.t)) continue;
+			d.prim = pi;
+			best = d;
+		}
+		hit[4 * k] = best.hit ? best.t : -1.f;
+		hit[4 * k + 1] = best.bu;
+		hit[4 * k + 2] = best.bv;
+		hit[4 * k + 3] = best.bw;
+		prim[k] = best.hit ? best.prim : -1;
+	}
+	return 0;
+}
+
+int yc_trace_shadow_exhaustive(const yc_scene *s, int n, const float *rays, int *occluded)
+{
+	Scene sc(*s);
+	const int n_tris = (int)sc.tris.size();
+	for(int k = 0; k < n; ++k)
+	{
+		const float *r = rays + 8 * k;
+		Ray ray;
+		ray.from = V3(r[0], r[1], r[2]);
+		ray.dir = V3(r[3], r[4], r[5]);
+		ray.tmin = r[6];
+		ray.tmax = r[7];
+		const float t_max = (ray.tmax >= 0.f) ? ray.tmax : std::numeric_limits<float>::infinity();
+		int occ = 0;
+		for(int pi = 0; pi < n_tris && !occ; ++pi)
+		{
+			const IsectData d = triIntersect(sc.tris[pi], ray);
+			if(d.hit && d.t >= 0.f && d.t < t_max) occ = 1;
+		}
+		occluded[k] = occ;
+	}
+	return 0;
+}
+
+// Per ray: the number of primitives that hit at exactly the closest t in [tmin, t_max) (0: a miss; 2 or more:
+// an exact tie, which the lower primitive index wins) — how many of a ray set's hits exercise the tie rule.
+int yc_trace_ties(const yc_scene *s, int n, const float *rays, int *n_equal)
+{
+	Scene sc(*s);
+	const int n_tris = (int)sc.tris.size();
+	for(int k = 0; k < n; ++k)
+	{
+		const float *r = rays + 8 * k;
+		Ray ray;
+		ray.from = V3(r[0], r[1], r[2]);
+		ray.dir = V3(r[3], r[4], r[5]);
+		ray.tmin = r[6];
+		ray.tmax = r[7];
+		const float t_max = (ray.tmax >= 0.f) ? ray.tmax : std::numeric_limits<float>::infinity();
+		float best = 0.f;
+		int count = 0;
+		for(int pi = 0; pi < n_tris; ++pi)
+		{
+			const IsectData d = triIntersect(sc.tris[pi], ray);
+			if(!d.hit || !(d.t >= ray.tmin && d.t < t_max)) continue;
+			if(count == 0 || d.t < best) { best = d.t; count = 1; }
+			else if(d.t == best) ++count;
+		}
+		n_equal[k] = count;
+	}
+	return 0;
+}
+
 void yc_riVdC(const uint32_t *bits, const uint32_t *r, float *out, int n) { for(int i = 0; i < n; ++i) out[i] = riVdC(bits[i], r[i]); }
 void yc_riS(const uint32_t *bits, const uint32_t *r, float *out, int n) { for(int i = 0; i < n; ++i) out[i] = riS(bits[i], r[i]); }
 void yc_riLp(const uint32_t *bits, const uint32_t *r, float *out, int n) { for(int i = 0; i < n; ++i) out[i] = riLp(bits[i], r[i]); }

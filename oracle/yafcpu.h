@@ -237,6 +237,11 @@ int yc_render_samples(const yc_scene *scene, int n, const int *xys, float *rgba)
 // hit out: 4 floats (t, bary_u, bary_v, bary_w) + prim index (-1 = miss).
 int yc_trace_closest(const yc_scene *scene, int n, const float *rays, float *hit, int *prim);
 int yc_trace_shadow(const yc_scene *scene, int n, const float *rays, int *occluded);
+// the same queries by a loop over every triangle (no BVH, no box test)
+int yc_trace_closest_exhaustive(const yc_scene *scene, int n, const float *rays, float *hit, int *prim);
+int yc_trace_shadow_exhaustive(const yc_scene *scene, int n, const float *rays, int *occluded);
+// per ray: how many primitives hit at exactly the closest t (>= 2: an exact tie between primitives)
+int yc_trace_ties(const yc_scene *scene, int n, const float *rays, int *n_equal);
 
 // Numeric building blocks (pinned against oracle/_ref).
 void yc_riVdC(const uint32_t *bits, const uint32_t *r, float *out, int n);

@@ -3,7 +3,8 @@
 Tolerances (BASELINE.json north_star: "radiance matches the reference CPU integrator within a
 stated float tolerance"):
   * ray level — closest-hit t and primitive bit-exact, shadow occlusion exact (exact-t ties
-    between different primitives resolve to the lower index in both; none occur here);
+    between different primitives resolve to the lower index in both; the vertex and edge classes of
+    tests/raylib.py produce them);
   * DirectLight and PathTracer without Russian roulette — per pixel |d| <= 4 ULP of the oracle
     value (the device emulates the reference's x87 products exactly, so in
     practice the images are bit-identical);
@@ -37,6 +38,21 @@ def random_rays(spec, n, seed):
     tmin = np.zeros((n, 1))
     tmax = np.where(rng.random((n, 1)) < 0.3, rng.random((n, 1)) * ext, -1.0)
     return np.concatenate([o, d, tmin, tmax], 1).astype(np.float32)
+
+
+def with_ray_classes(spec, rays, osc):
+    """`rays` plus every in-envelope class of tests/raylib.py (axis-parallel, vertex, edge, grazing, on-surface,
+    tmax-edge and per-octant rays; the tmax-edge class takes its hits from the oracle)."""
+    import raylib
+    extra = raylib.ray_classes(spec, lambda r: (lambda h, p: (h[:, 0].copy(), p))(*osc.trace_closest(r)))
+    return np.concatenate([rays] + [extra[c] for c in raylib.IN_ENVELOPE])
+
+
+def shadow_oracle(osc, rays):
+    """The oracle's any-hit query on the light rays as Accelerator::isShadowed prepares them (the origin moved by
+    tmin — the identity for the tmin = 0 rays of random_rays), which is what yafaray_amd_traceShadow answers."""
+    import raylib
+    return osc.trace_shadow(raylib.shadow_ray_of(rays))
 
 
 def product_scene(product, spec):
@@ -79,16 +95,16 @@ def test_trace_closest_and_shadow_bitexact(product, oracle_built, which, bvh, mo
     use_bvh(monkeypatch, bvh)
     spec = {"cornell": lambda: scenes.cornell(32, 32, spp=1), "test01": lambda: scenes.test01(32, 32, spp=1),
             "sphere": lambda: scenes.cornell_sphere(width=32, height=32, spp=1)}[which]()
-    rays = random_rays(spec, 20000, 7)
+    osc = oracle_built.OracleScene(spec)
+    rays = with_ray_classes(spec, random_rays(spec, 20000, 7), osc)
     yi = product_scene(product, spec)
     t, prim = yi.trace_closest(rays)
-    osc = oracle_built.OracleScene(spec)
     ohit, oprim = osc.trace_closest(rays)
     assert np.array_equal(prim, oprim), f"{(prim != oprim).sum()} primitive mismatches"
     hit = oprim >= 0
     assert np.array_equal(t[hit].view(np.uint32), ohit[hit, 0].view(np.uint32))
     occ = yi.trace_shadow(rays)
-    assert np.array_equal(occ, osc.trace_shadow(rays))
+    assert np.array_equal(occ, shadow_oracle(osc, rays))
     yi.close()
 
 
@@ -112,16 +128,16 @@ def test_gpu_bvh_build_small_and_ragged(product, oracle_built, n_tris, monkeypat
         spec = scenes.cornell_sphere(n=40, width=32, height=32, spp=1)
     else:
         spec = _subset(scenes.cornell(32, 32, spp=1), n_tris)
-    rays = random_rays(spec, 8000, 11)
+    osc = oracle_built.OracleScene(spec)
+    rays = with_ray_classes(spec, random_rays(spec, 8000, 11), osc)
     yi = product_scene(product, spec)
     t, prim = yi.trace_closest(rays)
-    osc = oracle_built.OracleScene(spec)
     ohit, oprim = osc.trace_closest(rays)
     assert np.array_equal(prim, oprim), f"{(prim != oprim).sum()} primitive mismatches"
     hit = oprim >= 0
     assert hit.any() or n_tris < 3
     assert np.array_equal(t[hit].view(np.uint32), ohit[hit, 0].view(np.uint32))
-    assert np.array_equal(yi.trace_shadow(rays), osc.trace_shadow(rays))
+    assert np.array_equal(yi.trace_shadow(rays), shadow_oracle(osc, rays))
     yi.close()
 
 
