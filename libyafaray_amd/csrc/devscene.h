@@ -471,6 +471,8 @@ struct DevQueues
 	// the overlapped schedule (render.cc iterate): neither changes a result
 	int trace_part;        // k_trace's plain loop: the ray kinds this launch traces (TRACE_*)
 	int nee_grid;          // k_nee workgroups (0 or >= n_seg: one per segment; fewer: a workgroup walks several segments)
+	int trace_defer;       // k_trace's plain no-spill BVH4 loop over an LDS-resident scene: 0 = leaf triangles tested inside
+	                       // the visit; n > 0 = recorded in per-lane LDS lists of n leaf entries and tested afterwards
 };
 
 // DevQueues::trace_part.  TRACE_CLOSEST reads no shadow count (k_nee may be writing it beside the launch);

@@ -997,6 +997,143 @@ __device__ bool traverse4(const TraceCtx &C, V3 o, V3 d, float tmin, float tmax,
 	return prim_best >= 0;
 }
 
+// traverse4 with the leaf triangle tests deferred (LDS-resident BVH4, no spill column, opaque shadows;
+// DevQueues::trace_defer).  traverse4 tests a hit leaf's triangles inside the visit, so a wave pays the
+// largest per-lane triangle count of every visit; here a visit only records its hit leaves in the lane's
+// list (LDS, [slot][lane], one 16-bit entry per leaf: first triangle slot in the low kDeferStartBits bits,
+// triangle count above), and the recorded triangles are tested afterwards in one dense loop per lane:
+//   phase 1: visits as in traverse4 (slab tests, box_t0, slack_t, child order, stack) while the lane is
+//            still traversing and its list has room for the four leaves a visit can add;
+//   phase 2: the lane's pending triangles through triTest and traverse4's hit predicates; an any-hit ray
+//            ends at its first hit, a closest hit tightens slack_t for the visits after a flush.
+// A lane leaves phase 1 because its own traversal ended or its own list is full, never because of a
+// neighbour, so a ray's visits and tests are a function of the ray and the capacity alone (the statistics
+// do not depend on how the waves are composed).  Box culling sees t_best only after a flush — a ray visits
+// a superset of traverse4's nodes — and the result is the same: closest hits are the minimum over
+// (t, primitive) of the tested triangles, any hits a boolean.
+constexpr int kDeferStartBits = 10;                      // scenes of < 1024 triangles (an LDS-resident scene holds <= 1024: 48 KB)
+constexpr int kDeferMaxLeaf = (1 << (16 - kDeferStartBits)) - 1;
+constexpr int kDeferRoom = 4;                            // free entries a visit needs (= the smallest capacity)
+template<bool ANY, bool STATS>
+__device__ bool traverse4Defer(const TraceCtx &C, uint16_t *list, int cap, V3 o, V3 d, float tmin, float tmax, float &t_best,
+                               int &prim_best, uint32_t &visits, uint32_t &tests)
+{
+#if !YAF_LANE_REMAT
+	const int lane = threadIdx.x;
+#endif
+	V3 dd = d;
+	if(fabsf(dd.x) < 1e-20f) dd.x = copysignf(1e-20f, dd.x);
+	if(fabsf(dd.y) < 1e-20f) dd.y = copysignf(1e-20f, dd.y);
+	if(fabsf(dd.z) < 1e-20f) dd.z = copysignf(1e-20f, dd.z);
+	const V3 id = v3(rcpExact(dd.x), rcpExact(dd.y), rcpExact(dd.z));
+	const V3 oid = v3(o.x * id.x, o.y * id.y, o.z * id.z);
+	const SlabSel sel = slabSel(id);
+	const float box_t0 = ANY ? -1e-3f : (tmin - 1e-3f * (1.f + fabsf(tmin)));
+	const float inf = __builtin_huge_valf();
+	t_best = tmax;
+	prim_best = -1;
+	int sp = 0;
+	int node = 0;   // -1: the traversal has ended
+	int n = 0;      // pending list entries
+	auto push = [&](int v) { C.stack[sp * kTraceBlock + YAF_LANE] = v; };
+	auto slackOf = [](float t) { return (t < 3.0e38f) ? t * 1.0000005f + 1e-6f : 3.4e38f; };
+	float slack_t = slackOf(t_best);
+	for(;;)
+	{
+		// ---- phase 1: box traversal, hit leaves recorded ----
+		while(node >= 0 && n + kDeferRoom <= cap)
+		{
+			if(STATS) TRACE_STAT(++visits);
+			const float4 *np = C.nodes + 8 * node;
+			const float4 nx = np[sel.nx], fx = np[sel.nx ^ 1], ny = np[sel.ny], fy = np[sel.ny ^ 1], nz = np[sel.nz], fz = np[sel.nz ^ 1], cf = np[6], kf = np[7];
+			float key[4];
+			int child[4];
+			uint16_t *lp = list + n * kTraceBlock + YAF_LANE;
+#pragma unroll
+			for(int k = 0; k < 4; ++k)
+			{
+				const float lo = fmaxf(fmaxf(__builtin_fmaf(lane4(nx, k), id.x, -oid.x), __builtin_fmaf(lane4(ny, k), id.y, -oid.y)),
+				                       fmaxf(__builtin_fmaf(lane4(nz, k), id.z, -oid.z), box_t0));
+				const float hi = fminf(fminf(__builtin_fmaf(lane4(fx, k), id.x, -oid.x), __builtin_fmaf(lane4(fy, k), id.y, -oid.y)),
+				                       fminf(__builtin_fmaf(lane4(fz, k), id.z, -oid.z), slack_t));
+				const uint32_t h = lo <= hi ? 1u : 0u;
+				child[k] = __float_as_int(lane4(cf, k));
+				const int count = __float_as_int(lane4(kf, k));
+				const uint32_t inner = child[k] >= 0 ? 1u : 0u;
+				key[k] = (h & inner) ? lo : inf;
+				// every child's entry is stored at the lane's next slot and kept only where the child is a hit
+				// leaf (the slot then advances; n + 4 <= cap holds on entry): no lane-varying branch per child
+				const uint32_t leaf = h & (inner ^ 1u) & (count > 0 ? 1u : 0u);
+				*lp = (uint16_t)((uint32_t)~child[k] | ((uint32_t)count << kDeferStartBits));
+				lp += leaf ? kTraceBlock : 0;
+				n += (int)leaf;
+			}
+			int next;
+			if constexpr(ANY && !YAF_ANY_SORT)
+			{
+				next = -1;
+#pragma unroll
+				for(int k = 0; k < 4; ++k)
+				{
+					if(!(key[k] < inf)) continue;
+					if(next < 0) next = child[k];
+					else { push(child[k]); ++sp; }
+				}
+			}
+			else
+			{
+				cswap(key[0], child[0], key[1], child[1]);
+				cswap(key[2], child[2], key[3], child[3]);
+				cswap(key[0], child[0], key[2], child[2]);
+				cswap(key[1], child[1], key[3], child[3]);
+				cswap(key[1], child[1], key[2], child[2]);
+				if(key[3] < inf) { push(child[3]); ++sp; }
+				if(key[2] < inf) { push(child[2]); ++sp; }
+				if(key[1] < inf) { push(child[1]); ++sp; }
+				next = key[0] < inf ? child[0] : -1;
+			}
+			if(next < 0 && sp > 0)
+			{
+				--sp;
+				next = C.stack[sp * kTraceBlock + YAF_LANE];
+			}
+			node = next;
+		}
+		// ---- phase 2: the pending leaves' triangles, one per trip whatever leaf they belong to ----
+		// (last recorded leaf first: n is the loop's only index, and no result depends on the order)
+		uint32_t ent = 0;   // the leaf being tested: next triangle slot | triangles left << kDeferStartBits
+		for(;;)
+		{
+			if((ent >> kDeferStartBits) == 0)
+			{
+				if(n == 0) break;
+				--n;
+				ent = list[n * kTraceBlock + YAF_LANE];
+			}
+			if(STATS) TRACE_STAT(++tests);
+			const float4 *tp = C.tris + 3 * (ent & ((1u << kDeferStartBits) - 1u));
+			const float4 ta = tp[0], tb = tp[1], tc = tp[2];
+			ent += 1u - (1u << kDeferStartBits);   // (the slot of a leaf's last triangle + 1 <= 1023: no carry into the count)
+			const float t = triTest(ta, tb, tc, o, d, ANY ? tmax : t_best);
+			if(t == -1.f) continue;
+			const int prim = __float_as_int(tb.w);
+			if(ANY)
+			{
+				if(t < tmax && t >= 0.f) { t_best = t; prim_best = prim; node = -1; break; }
+			}
+			else if(t >= tmin && (t < t_best || (t == t_best && prim_best >= 0 && prim < prim_best)))
+			{
+				t_best = t;
+				prim_best = prim;
+				slack_t = slackOf(t_best);
+			}
+		}
+		n = 0;
+		if(node < 0) break;
+	}
+	return prim_best >= 0;
+}
+
 // k_trace's BVH4 loop with per-lane ray refill: a lane works through its own sequence of queue
 // entries (j, j + stride, ...), closest rays then shadow rays, and starts its next ray as soon as
 // its traversal ends, so a wave runs as long as its longest lane's sum of rays instead of the sum
@@ -1505,10 +1642,12 @@ __device__ __forceinline__ void waveSortWindow(WaveSort &W, const uint32_t (&key
 // rendered with them — the frame is deterministic, so they are the same)
 // SORT: ray-stream sorting of each wave's window (above)
 // W8: the refill loop over the BVH8 (S.nodes8; global-memory scenes without transparent shadows)
-template<bool LDS_SCENE, bool WIDE, bool TS, bool SPILL = true, bool STATS = true, bool SORT = false, bool W8 = false>
+// DEFER: the plain loop's BVH4 traversal with deferred leaf tests (traverse4Defer; Q.trace_defer = the lists' capacity)
+template<bool LDS_SCENE, bool WIDE, bool TS, bool SPILL = true, bool STATS = true, bool SORT = false, bool W8 = false, bool DEFER = false>
 __global__ void __launch_bounds__(kTraceBlock) YAF_TRACE_ATTR k_trace(DevScene S, DevQueues Q, DevCounters cnt, DevPaths P,
                                                       DevStats *stats, int stack_depth, int *spill)
 {
+	static_assert(!DEFER || (LDS_SCENE && WIDE && !TS && !SPILL && !SORT && !W8), "deferred leaf tests: the plain no-spill BVH4 loop of LDS-resident scenes");
 	extern __shared__ float4 smem[];
 	int *stack = reinterpret_cast<int *>(smem);
 	TraceCtx C;
@@ -1517,6 +1656,7 @@ __global__ void __launch_bounds__(kTraceBlock) YAF_TRACE_ATTR k_trace(DevScene S
 	C.lds_depth = stack_depth;
 	C.spill = spill;
 	C.spill_stride = gridDim.x * blockDim.x;
+	uint16_t *dlist = nullptr;
 	if(LDS_SCENE)
 	{
 		float4 *lds_nodes = smem + (stack_depth * kTraceBlock) / 4;
@@ -1526,6 +1666,8 @@ __global__ void __launch_bounds__(kTraceBlock) YAF_TRACE_ATTR k_trace(DevScene S
 		__syncthreads();
 		C.nodes = lds_nodes;
 		C.tris = lds_tris;
+		// the deferred leaf lists, [slot][lane], behind the scene
+		if constexpr(DEFER) dlist = reinterpret_cast<uint16_t *>(lds_tris + 3 * S.n_tris);
 	}
 	else
 	{
@@ -1584,7 +1726,8 @@ __global__ void __launch_bounds__(kTraceBlock) YAF_TRACE_ATTR k_trace(DevScene S
 				float t;
 				int prim;
 				const float tmax = (tw >= 0.f) ? tw : __builtin_huge_valf();
-				traverse<false, WIDE, SPILL, false, STATS, LDS_SCENE>(C, o, d, tmin, tmax, t, prim, visits, tests);
+				if constexpr(DEFER) traverse4Defer<false, STATS>(C, dlist, Q.trace_defer, o, d, tmin, tmax, t, prim, visits, tests);
+				else traverse<false, WIDE, SPILL, false, STATS, LDS_SCENE>(C, o, d, tmin, tmax, t, prim, visits, tests);
 				raySt(&Q.hit_t[i], t);
 				raySt(&Q.hit_prim[i], prim);
 				return 1;
@@ -1608,6 +1751,7 @@ __global__ void __launch_bounds__(kTraceBlock) YAF_TRACE_ATTR k_trace(DevScene S
 				occ = traverse<true, WIDE, SPILL, true>(C, xyz(od), xyz(dd), od.w, dd.w, t, prim, visits, tests, &L);
 				Q.ts_n[k] = occ ? 0 : L.n;
 			}
+			else if constexpr(DEFER) occ = traverse4Defer<true, STATS>(C, dlist, Q.trace_defer, xyz(od), xyz(dd), 0.f, dd.w, t, prim, visits, tests);
 			else occ = traverse<true, WIDE, SPILL, false, STATS>(C, xyz(od), xyz(dd), 0.f, dd.w, t, prim, visits, tests);
 			// (opaque shadows: the NEE entry index rides in sh_o.w)
 			P.occ[TS ? Q.sh_idx[k] : __float_as_int(od.w)] = occ ? 1 : 0;   // P = state set of the consumer shade
@@ -7355,12 +7499,19 @@ int yafamd_phase_cycles(unsigned long long *out, int n, int reset)
 #endif
 }
 
+// Whether traverse4Defer's 16-bit leaf entries can describe a tree of n_tris triangles with leaves of at most
+// max_leaf triangles, and the smallest list capacity (render.cc sizes the lists: 2 B per slot and lane)
+int yafamd_trace_defer_ok(int n_tris, int max_leaf) { return n_tris < (1 << kDeferStartBits) && max_leaf <= kDeferMaxLeaf; }
+int yafamd_trace_defer_min_cap() { return kDeferRoom; }
+
 // Resident workgroups per CU of the persistent kernels (their grids fill the chip exactly once).
-int yafamd_trace_blocks_per_cu(int lds_scene, int wide, size_t dyn_lds)
+int yafamd_trace_blocks_per_cu(int lds_scene, int wide, size_t dyn_lds, int defer)
 {
 	int nb = 0;
 	hipError_t e;
-	if(wide == 8) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace<false, true, false, true, false, false, true>, kTraceBlock, dyn_lds);
+	// (defer: the deferred-leaf kernel, whose dyn_lds counts the lists)
+	if(defer) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace<true, true, false, false, false, false, false, true>, kTraceBlock, dyn_lds);
+	else if(wide == 8) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace<false, true, false, true, false, false, true>, kTraceBlock, dyn_lds);
 	else if(lds_scene) e = wide ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace<true, true, false>, kTraceBlock, dyn_lds)
 	                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace<true, false, false>, kTraceBlock, dyn_lds);
 	else e = wide ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace<false, true, false>, kTraceBlock, dyn_lds)
@@ -7411,7 +7562,7 @@ hipError_t yafamd_launch_trace(const DevScene *S, const DevQueues *Q, const DevC
 	const bool wide = S->node_f4 == 8;
 	const size_t lds_scene = S->scene_in_lds ? (size_t)(S->node_f4 * S->n_nodes + 3 * S->n_tris) * sizeof(float4)
 	                                         : (wide ? (size_t)S->lds_top * kTopStride * sizeof(float4) : 0);
-	const size_t bytes = stack_bytes + lds_scene;
+	size_t bytes = stack_bytes + lds_scene;
 	if(S->nodes8 && !S->scene_in_lds && !S->tr_shad)
 	{
 		// the BVH8 refill loop (global-memory scenes; its top treelet instead of the BVH4's)
@@ -7459,7 +7610,20 @@ hipError_t yafamd_launch_trace(const DevScene *S, const DevQueues *Q, const DevC
 		}
 		else
 #endif
-		if(nospill && wide && !S->trace_stats)
+		if(nospill && wide && Q->trace_defer > 0)
+		{
+			// deferred leaf tests (traverse4Defer): the lists follow the scene.  The caller sets trace_defer only
+			// for trees whose leaves fit an entry (yafamd_trace_defer_ok with the builder's largest leaf)
+			if(Q->trace_defer < kDeferRoom || S->n_tris >= (1 << kDeferStartBits)) return hipErrorInvalidValue;
+			bytes += (size_t)Q->trace_defer * kTraceBlock * sizeof(uint16_t);
+			if(S->trace_stats)
+				hipLaunchKernelGGL((k_trace<true, true, false, false, true, false, false, true>), dim3(grid), dim3(kTraceBlock), bytes, st, *S, *Q, *cnt, *P, stats,
+				                   stack_depth, spill);
+			else
+				hipLaunchKernelGGL((k_trace<true, true, false, false, false, false, false, true>), dim3(grid), dim3(kTraceBlock), bytes, st, *S, *Q, *cnt, *P, stats,
+				                   stack_depth, spill);
+		}
+		else if(nospill && wide && !S->trace_stats)
 			hipLaunchKernelGGL((k_trace<true, true, false, false, false>), dim3(grid), dim3(kTraceBlock), bytes, st, *S, *Q, *cnt, *P, stats,
 			                   stack_depth, spill);
 		else if(nospill) { if(wide) YAF_TRACE_LAUNCH(true, true, false, false); else YAF_TRACE_LAUNCH(true, false, false, false); }

@@ -38,7 +38,9 @@ int yafamd_walk_lds_levels(int pm_stack);
 int yafamd_walk_threads(const DevScene *S);
 int yafamd_shade_fused_for(const DevScene *S);
 int yafamd_experiments();
-int yafamd_trace_blocks_per_cu(int lds_scene, int wide, size_t dyn_lds);
+int yafamd_trace_blocks_per_cu(int lds_scene, int wide, size_t dyn_lds, int defer);
+int yafamd_trace_defer_ok(int n_tris, int max_leaf);
+int yafamd_trace_defer_min_cap();
 int yafamd_shade_blocks_per_cu();
 hipError_t yafamd_launch_shade(const DevScene *S, const DevPaths *Pc, const DevPaths *Pn, const DevQueues *Q,
                                const DevQueues *Qn, const DevNeeQueue *N, const DevNeeQueue *G, const DevCounters *cnt,
@@ -125,6 +127,17 @@ hipError_t yafamd_launch_layer_film(const DevFilm *F, const DevLayers *L, const 
 
 namespace
 {
+
+// k_trace's deferred leaf tests where YAFARAY_AMD_TRACE_DEFER does not decide (profiles/c2_trace_deferred.md)
+constexpr bool kTraceDeferDefault = true;
+// DevQueues::trace_defer of a scene whose lists hold `cap` leaves (0: not eligible): YAFARAY_AMD_TRACE_DEFER=0 / 1
+// decides for every eligible scene, read per render and per traceQueued call, as S.ray_sort / S.brute are
+int traceDeferCap(int cap)
+{
+	bool on = kTraceDeferDefault;
+	if(const char *e = std::getenv("YAFARAY_AMD_TRACE_DEFER"); e && *e) on = *e != '0';
+	return on ? cap : 0;
+}
 
 // The renderer's device made current for the duration of a call; the caller's device is restored
 // (several renderers of one process, on different devices, may be driven from one thread).
@@ -347,6 +360,7 @@ struct GpuRenderer::Impl
 	uint32_t pm_local = 0;   // diffuse photon paths this member shot (its share in a group render)
 	int n_nodes = 0, n_tris = 0, n_mats = 0, n_lights = 0, depth = 0, stack_depth = 32, node_f4 = 4;
 	int lds_stack = 32;    // k_trace stack levels held in LDS; levels [lds_stack, stack_depth) spill to `spill`
+	int trace_defer = 0;   // k_trace's deferred leaf tests: the per-lane list's capacity for this scene (0: not eligible)
 	Buf spill;
 	bool scene_in_lds = false;
 	int lds_top = 0;   // BVH4 in global memory: nodes k_trace stages in LDS (the top treelet)
@@ -877,7 +891,27 @@ bool GpuRenderer::upload(HostScene &hs)
 		const bool w8 = d.nodes8.p && !d.scene_in_lds;
 		const size_t dyn = (size_t)d.lds_stack * yafamd_trace_block() * 4 +
 		                   (d.scene_in_lds ? scene_bytes : w8 ? (size_t)d.lds_top8 * 80 : (size_t)d.lds_top * 144);
-		d.trace_grid = d.n_cu * std::max(1, yafamd_trace_blocks_per_cu(d.scene_in_lds ? 1 : 0, w8 ? 8 : (d.node_f4 == 8 ? 1 : 0), dyn));
+		const int per_cu = std::max(1, yafamd_trace_blocks_per_cu(d.scene_in_lds ? 1 : 0, w8 ? 8 : (d.node_f4 == 8 ? 1 : 0), dyn, 0));
+		d.trace_grid = d.n_cu * per_cu;
+		// Deferred leaf tests in k_trace's plain BVH4 loop (kernels.hip traverse4Defer): LDS-resident
+		// scenes without a spill column whose leaves fit the 16-bit list entries.  The per-lane lists (2 B per
+		// entry and lane) follow the scene in LDS and never cost a resident workgroup: the capacity
+		// (YAFARAY_AMD_TRACE_DEFER_CAP, default 8 leaves) shrinks until the kernel keeps the grid above, and a scene
+		// without room for the smallest list keeps the interleaved loop.  Whether a launch uses the lists is read
+		// per render (traceDeferCap below).
+		d.trace_defer = 0;
+		{
+			if(d.scene_in_lds && d.node_f4 == 8 && d.lds_stack >= d.stack_depth && yafamd_trace_defer_ok(d.n_tris, hs.bvh.max_leaf))
+			{
+				const int min_cap = yafamd_trace_defer_min_cap();
+				int cap = 8;
+				if(const char *e = getenv("YAFARAY_AMD_TRACE_DEFER_CAP"); e && *e) cap = atoi(e);
+				cap = std::min(std::max(cap, min_cap), 64);
+				auto fits = [&](int c) { return yafamd_trace_blocks_per_cu(1, 1, dyn + (size_t)c * yafamd_trace_block() * 2, 1) >= per_cu; };
+				while(cap > min_cap && !fits(cap)) cap = std::max(min_cap, cap - 2);
+				if(fits(cap)) d.trace_defer = cap;
+			}
+		}
 		if(const char *e = getenv("YAFARAY_AMD_TRACE_GRID")) d.trace_grid = std::max(1, atoi(e));
 		// a whole number of workgroups per queue segment
 		d.trace_grid = std::max(1, d.trace_grid / d.shade_grid) * d.shade_grid;
@@ -887,7 +921,7 @@ bool GpuRenderer::upload(HostScene &hs)
 		if(w8 && !getenv("YAFARAY_AMD_TRACE_GRID"))
 		{
 			const size_t dyn4 = (size_t)d.lds_stack * yafamd_trace_block() * 4 + (size_t)d.lds_top * 144;
-			int g4 = d.n_cu * std::max(1, yafamd_trace_blocks_per_cu(0, d.node_f4 == 8 ? 1 : 0, dyn4));
+			int g4 = d.n_cu * std::max(1, yafamd_trace_blocks_per_cu(0, d.node_f4 == 8 ? 1 : 0, dyn4, 0));
 			g4 = std::max(1, g4 / d.shade_grid) * d.shade_grid;
 			d.trace_grid_bvh4 = std::min(g4, d.trace_grid);
 		}
@@ -2380,6 +2414,14 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_SHADOW_GRID"); e && atoi(e) > 0)
 		ov_shadow_grid = (int)S.n_seg * std::max(1, std::min(atoi(e), d.trace_grid) / (int)S.n_seg);
 	ov_shadow = ov_shadow && overlap && d.spill.p == nullptr;
+	// k_trace's deferred leaf tests (upload() decided the capacity): every launch of the render, full or part,
+	// timed or with statistics, runs the same traversal.  Iteration 0 keeps the interleaved loop under either
+	// schedule: the coherent camera rays of a wave hit the same leaves at the same visits, so the lists only add
+	// their bookkeeping (C2: 2.0 -> 2.4 ms for that launch, profiles/c2_trace_deferred.md);
+	// YAFARAY_AMD_TRACE_DEFER_IT0=1 uses the lists there too (A/B)
+	d.Q[0].trace_defer = d.Q[1].trace_defer = traceDeferCap(d.trace_defer);
+	bool defer_it0 = false;
+	if(const char *e = std::getenv("YAFARAY_AMD_TRACE_DEFER_IT0"); e && *e) defer_it0 = *e != '0';
 	// The megakernel (k_path, kernels.hip; opt-in YAFARAY_AMD_PATH=mega) for scenes whose BVH, stack
 	// and tables live in LDS and need none of the wavefront-only stages (EXT shading, transparent
 	// shadows, photon maps, AO): one lane per sample, the same functions in the same order, the film
@@ -2458,6 +2500,7 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 			qc.tmin_dflt = it == 0 ? 0.f : S.ray_min_dist;
 			qc.perm = nullptr;
 			qc.trace_part = closest_done ? TRACE_SHADOW : TRACE_BOTH;
+			if(it == 0 && !defer_it0) qc.trace_defer = 0;
 			// the side stream's closest part is still running: the shadow part goes beside it, then the join
 			const bool join_pending = closest_done && ov_shadow;
 			closest_done = false;
@@ -3404,6 +3447,7 @@ bool GpuRenderer::traceRaysQueued(const float *closest, int n_closest, const flo
 		Q.sh_d = (float4 *)b_sd.p;
 		Q.perm = nullptr;
 		Q.trace_part = part;
+		Q.trace_defer = traceDeferCap(d.trace_defer);
 		DevCounters cnt{};
 		cnt.n_active = (uint32_t *)b_na.p;
 		cnt.n_shadow = (uint32_t *)b_ns.p;
