@@ -425,7 +425,7 @@ struct DevPaths
 	float4 *col;           // col (first-vertex estimate), .w = stage | subpath << 8 | depth << 20 (bits)
 	float4 *pcol;          // path_col, .w = flags: mat_bsd_fs (v1 flags) | bits below (bits)
 	float4 *pwo;           // pwo (outgoing direction at the current path vertex): ST_FIRST entries without F_SAMPLED only
-	float4 *pend_thr;      // throughput at the pending vertex (after Russian roulette), 12 B per entry (kernels.hip F3)
+	float4 *pend_thr;      // throughput at the pending vertex (after Russian roulette), 12 B per entry (trace.h F3)
 	float4 *pend_emit;     // emission pending at that vertex
 	float4 *v0p;           // first hit p .w = prim (bits)   — only used when path_samples > 1
 	float4 *v0wo;          // first hit wo

@@ -33,14 +33,13 @@
 #include "devmath.h"
 #include "photonheap.h"
 #include "devscene.h"
+#include "trace.h"
 #include "texeval.h"
 
 namespace yafamd
 {
 
-#ifndef YAF_TRACE_BLOCK
-#define YAF_TRACE_BLOCK 128
-#endif
+// (YAF_TRACE_BLOCK / kTraceBlock, the BVH traversal and the queues' ray accessors: trace.h)
 // k_shade / k_nee (non-EXT instantiations): at least 4 waves per SIMD (<= 128 VGPRs; the unconstrained allocation took
 // 132 / 143 and 3 waves).  Measured on C2: 1400 -> 1500 Msamples/s (shade 0.70 -> 0.62 ms per
 // launch, NEE 17.7 -> 15.6 ms per frame), -DYAF_*_MIN_WAVES=n overrides for tuning
@@ -53,7 +52,6 @@ namespace yafamd
 #ifndef YAF_SHADE_PREFETCH
 #define YAF_SHADE_PREFETCH 1
 #endif
-constexpr int kTraceBlock = YAF_TRACE_BLOCK;
 // -DYAF_EXPERIMENTS: the pipelines measured and dropped stay buildable for re-measurement but out of
 // the product library (kExperiments; yafaray_amd_buildInfo records the flag): k_trace_brute, ray-stream
 // sorting in k_trace, the megakernel k_path, k_nee tracing its shadow rays in place, the bounded-radius
@@ -117,7 +115,6 @@ enum : uint32_t
 
 __device__ __forceinline__ float u2f(uint32_t u) { return __uint_as_float(u); }
 __device__ __forceinline__ uint32_t f2u(float f) { return __float_as_uint(f); }
-__device__ __forceinline__ V3 xyz(const float4 &a) { return v3(a.x, a.y, a.z); }
 __device__ __forceinline__ C3 rgb(const float4 &a) { return C3{a.x, a.y, a.z}; }
 __device__ __forceinline__ float4 f4(V3 v, float w) { return make_float4(v.x, v.y, v.z, w); }
 __device__ __forceinline__ float4 f4(C3 c, float w) { return make_float4(c.r, c.g, c.b, w); }
@@ -191,73 +188,6 @@ __device__ __forceinline__ void stStore2(T *p, const T &v)
 #endif
 }
 
-// 12-byte records (one dwordx3 per lane, 4-byte aligned): the pending throughput, whose fourth
-// component was never read
-struct F3
-{
-	float x, y, z;
-};
-
-// Closest-ray queue entry i (DevQueues::ray_o / ray_d: 12-B records, 24 B per ray instead of 32):
-// false when the entry carries no ray this iteration (NaN direction x).  tmin / tmax (< 0:
-// infinite) come from ray_tt in a pass's first iteration when its rays carry their own (spawned rays;
-// camera rays with clip planes), else (Q.tmin_dflt, infinite): camera rays 0, k_shade's bounces
-// ray_min_dist.
-// -DYAF_NT_RAYLOAD=1: the ray streams of k_trace are loaded / stored non-temporally (streaming
-// lines evicted first: the node working set of a BVH in global memory keeps more of the L2)
-#ifndef YAF_NT_RAYLOAD
-#define YAF_NT_RAYLOAD 0
-#endif
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ F3 rayLd3(const float *p, uint32_t i)
-{
-#if YAF_NT_RAYLOAD
-	const float *q = p + 3 * (size_t)i;
-	return F3{__builtin_nontemporal_load(q), __builtin_nontemporal_load(q + 1), __builtin_nontemporal_load(q + 2)};
-#else
-	return reinterpret_cast<const F3 *>(p)[i];
-#endif
-}
-__device__ __forceinline__ float4 rayLd4(const float4 *p)
-{
-#if YAF_NT_RAYLOAD
-	const f32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t *>(p));
-	return make_float4(v.x, v.y, v.z, v.w);
-#else
-	return *p;
-#endif
-}
-template<class T>
-__device__ __forceinline__ void raySt(T *p, T v)
-{
-#if YAF_NT_RAYLOAD
-	__builtin_nontemporal_store(v, p);
-#else
-	*p = v;
-#endif
-}
-
-__device__ __forceinline__ bool loadQRay(const DevQueues &Q, uint32_t i, V3 &o, V3 &d, float &tmin, float &tmax_w)
-{
-	// (both records loaded before the test: one memory round trip, not two dependent ones)
-	const F3 dd = rayLd3(Q.ray_d, i);
-	const F3 oo = rayLd3(Q.ray_o, i);
-	d = v3(dd.x, dd.y, dd.z);
-	o = v3(oo.x, oo.y, oo.z);
-	if(dd.x != dd.x) return false;
-	if(Q.ray_tt)
-	{
-		const float2 tt = Q.ray_tt[i];
-		tmin = tt.x;
-		tmax_w = tt.y;
-	}
-	else
-	{
-		tmin = Q.tmin_dflt;
-		tmax_w = -1.f;
-	}
-	return true;
-}
 typedef float f32x3a4_t __attribute__((ext_vector_type(3))) __attribute__((aligned(4)));
 __device__ __forceinline__ void storeQRay(const DevQueues &Q, uint32_t i, V3 o, V3 d)
 {
@@ -572,980 +502,8 @@ __global__ void __launch_bounds__(256) k_camera(DevScene S, DevPaths P, DevQueue
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_trace: BVH2 / BVH4 traversal
+// k_trace: the queued closest and shadow rays through the traversal loops of trace.h
 // ---------------------------------------------------------------------------------------------
-#ifndef YAF_TOP_STRIDE
-#define YAF_TOP_STRIDE 9
-#endif
-constexpr int kTopStride = YAF_TOP_STRIDE;
-#ifndef YAF_LANE_REMAT
-#define YAF_LANE_REMAT 1
-#endif   // float4 per node of the LDS top treelet (8 used + 1 pad)
-struct TraceCtx
-{
-	const float4 *nodes;
-	const float4 *tris;
-	int *stack;     // LDS, [level * kTraceBlock + lane], levels [0, lds_depth)
-	int lds_depth;
-	int *spill;     // HBM, [(level - lds_depth) * spill_stride + global lane] (BVH4 deep levels)
-	uint32_t spill_stride;
-	// the top treelet of a BVH4 in global memory staged in LDS: nodes [0, n_top) at kTopStride float4 each
-	// (144 B: a 128-B stride put every node's plane p on the same 4 of the 64 banks, so the 16 lanes of a
-	// ds_read_b128 group at different nodes conflicted up to 8-way; 36-dword strides spread 16 nodes
-	// over 16 distinct bank quads) (both builders number
-	// the wide nodes level by level, so these are the levels every ray starts with)
-	const float4 *top = nullptr;
-	int n_top = 0;
-	uint32_t wave_base = 0;   // threadIdx.x of the wave's lane 0 (scalar; set with the context: waveBase())
-};
-// threadIdx.x of the wave's first lane, and this lane's threadIdx.x re-derived from it (v_mbcnt, opaque so
-// that it is recomputed where used instead of keeping threadIdx.x live — or spilled — across the loops)
-__device__ __forceinline__ uint32_t waveBase() { return __builtin_amdgcn_readfirstlane((uint32_t)threadIdx.x) & ~63u; }
-__device__ __forceinline__ uint32_t tidFrom(uint32_t wave_base)
-{
-	uint32_t l;
-	asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-	return wave_base + l;
-}
-
-// Transparent-shadow hit list of one shadow ray (accelerator_kdtree.cc:1001-1023): an opaque
-// surface shadows; each transparent one is recorded until `cap` (= shadowDepth) are recorded, the
-// next one shadows.  A BVH holds every triangle once, so the reference's `filtered` set (one
-// factor per primitive) needs no lookup.
-struct TsList
-{
-	float2 *hit;
-	int n, cap;
-	const float4 *prim_ng;
-	const DevMaterial *mats;
-};
-
-__device__ __forceinline__ bool tsShadows(TsList &L, float t, int prim)
-{
-	const int mat = __float_as_int(L.prim_ng[prim].w);
-	if(!(L.mats[mat].sd_flags & SD_TRANSPARENT)) return true;
-	if(L.n >= L.cap) return true;
-	L.hit[L.n] = make_float2(t, __int_as_float(prim));
-	++L.n;
-	return false;
-}
-
-__device__ __forceinline__ void boxPair(const float4 &n0, const float4 &n1, const float4 &n2, V3 o, V3 id,
-                                        float t0, float t1, bool &h0, bool &h1, float &tn0, float &tn1)
-{
-	// child 0
-	float ax = (n0.x - o.x) * id.x, bx = (n0.y - o.x) * id.x;
-	float ay = (n0.z - o.y) * id.y, by = (n0.w - o.y) * id.y;
-	float az = (n2.x - o.z) * id.z, bz = (n2.y - o.z) * id.z;
-	float lo = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), t0));
-	float hi = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), t1));
-	h0 = lo <= hi;
-	tn0 = lo;
-	ax = (n1.x - o.x) * id.x; bx = (n1.y - o.x) * id.x;
-	ay = (n1.z - o.y) * id.y; by = (n1.w - o.y) * id.y;
-	az = (n2.z - o.z) * id.z; bz = (n2.w - o.z) * id.z;
-	lo = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), t0));
-	hi = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), t1));
-	h1 = lo <= hi;
-	tn1 = lo;
-}
-
-// primitive_triangle.cc:44-71.  Returns t or -1.  The reference's arithmetic (correctly rounded
-// 1/det, then products) evaluated branch-free: every lane computes the same instruction stream
-// and the reference's early returns become one combined predicate (NaN comparisons keep their
-// reference outcome).  `t_cut` is unused by the exact test.  (The short-circuit form is kept on
-// purpose: the compiler turns it into det -> u -> (v, t) early outs; a bitwise predicate that
-// computes every term measured k_trace 27.6 -> 35.4 ms per C2 frame.)
-// Correctly rounded 1/x: v_rcp_f32 + one FMA Newton step, which tools/rcp_check.hip
-// verified exhaustively on gfx950 to equal the IEEE quotient for every float with
-// 2^-125 <= |x| <= 2^125 (other magnitudes, zero, inf and NaN take the IEEE division).
-__device__ __forceinline__ float rcpExact(float x)
-{
-	const float ax = fabsf(x);
-	if(ax >= 0x1p-125f && ax <= 0x1p125f)
-	{
-		const float y = __builtin_amdgcn_rcpf(x);
-		return __builtin_fmaf(y, __builtin_fmaf(-x, y, 1.f), y);
-	}
-	return 1.f / x;
-}
-
-__device__ __forceinline__ float triTest(const float4 &a, const float4 &b, const float4 &c, V3 o, V3 d, float t_cut)
-{
-	(void)t_cut;
-	const V3 v0 = xyz(a), e1 = xyz(b), e2 = xyz(c);
-	const float eps = a.w;
-	const V3 pvec = cross(d, e2);
-	const float det = dot(e1, pvec);
-	const float inv_det = rcpExact(det);
-	const V3 tvec = o - v0;
-	const float u = dot(tvec, pvec) * inv_det;
-	const V3 qvec = cross(tvec, e1);
-	const float v = dot(d, qvec) * inv_det;
-	const float t = dot(e2, qvec) * inv_det;
-	const bool miss = (det > -eps && det < eps) || (u < 0.f || u > 1.f) || (v < 0.f) || ((u + v) > 1.f) || (t < eps);
-	return miss ? -1.f : t;
-}
-
-// per-visit statistics of the traversal (node visits, triangle tests); -DYAF_TRACE_NOSTATS drops them
-#ifdef YAF_TRACE_NOSTATS
-#define TRACE_STAT(x) do {} while(0)
-#else
-#define TRACE_STAT(x) x
-#endif
-
-// Closest hit with t in [tmin, tmax) (ties -> lower primitive index), or any hit with t in
-// [0, tmax).  Box tests are conservative (boxes padded at build time + a relative slack), so
-// culling never drops a hit the exhaustive reference semantics would return.
-template<bool ANY, bool TS = false, bool STATS = true>
-__device__ bool traverse2(const TraceCtx &C, V3 o, V3 d, float tmin, float tmax, float &t_best, int &prim_best,
-                          uint32_t &visits, uint32_t &tests, TsList *ts = nullptr)
-{
-	const int lane = threadIdx.x;
-	V3 dd = d;
-	if(fabsf(dd.x) < 1e-20f) dd.x = copysignf(1e-20f, dd.x);
-	if(fabsf(dd.y) < 1e-20f) dd.y = copysignf(1e-20f, dd.y);
-	if(fabsf(dd.z) < 1e-20f) dd.z = copysignf(1e-20f, dd.z);
-	const V3 id = v3(rcpExact(dd.x), rcpExact(dd.y), rcpExact(dd.z));
-	const float box_t0 = ANY ? -1e-3f : (tmin - 1e-3f * (1.f + fabsf(tmin)));
-	t_best = tmax;
-	prim_best = -1;
-	int sp = 0;
-	int node = 0;
-	for(;;)
-	{
-		if(STATS) TRACE_STAT(++visits);
-		const float4 *np = C.nodes + 4 * node;
-		const float4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
-		const float slack_t = (t_best < 3.0e38f) ? t_best * 1.0000005f + 1e-6f : 3.4e38f;
-		bool h0, h1;
-		float tn0, tn1;
-		boxPair(n0, n1, n2, o, id, box_t0, slack_t, h0, h1, tn0, tn1);
-		const int c0 = __float_as_int(n3.x), c1 = __float_as_int(n3.y);
-		const int k0 = __float_as_int(n3.z), k1 = __float_as_int(n3.w);
-		int next = -1;
-		// leaves are tested right away; inner children are descended nearest-first
-#pragma unroll
-		for(int side = 0; side < 2; ++side)
-		{
-			const bool h = side ? h1 : h0;
-			const int c = side ? c1 : c0;
-			const int k = side ? k1 : k0;
-			if(!h || c >= 0 || k == 0) continue;
-			const int start = ~c;
-			for(int q = start; q < start + k; ++q)
-			{
-				if(STATS) TRACE_STAT(++tests);
-				const float4 *tp = C.tris + 3 * q;
-				const float4 ta = tp[0], tb = tp[1], tc = tp[2];
-				const float t = triTest(ta, tb, tc, o, d, ANY ? tmax : t_best);
-				if(t == -1.f) continue;
-				const int prim = __float_as_int(tb.w);
-				if(ANY && TS)
-				{
-					// intersectTs: t in [tmin, t_max) of the moved ray (tmin kept, accelerator.cc:82-85)
-					if(t < tmax && t >= tmin && tsShadows(*ts, t, prim)) { t_best = t; prim_best = prim; return true; }
-				}
-				else if(ANY)
-				{
-					if(t < tmax && t >= 0.f) { t_best = t; prim_best = prim; return true; }
-				}
-				else if(t >= tmin && (t < t_best || (t == t_best && prim_best >= 0 && prim < prim_best)))
-				{
-					t_best = t;
-					prim_best = prim;
-				}
-			}
-		}
-		const bool i0 = h0 && c0 >= 0, i1 = h1 && c1 >= 0;
-		if(i0 && i1)
-		{
-			const bool first0 = tn0 <= tn1;
-			next = first0 ? c0 : c1;
-			C.stack[sp * kTraceBlock + lane] = first0 ? c1 : c0;
-			++sp;
-		}
-		else if(i0) next = c0;
-		else if(i1) next = c1;
-		if(next < 0)
-		{
-			if(sp == 0) break;
-			--sp;
-			next = C.stack[sp * kTraceBlock + lane];
-		}
-		node = next;
-	}
-	return prim_best >= 0;
-}
-
-__device__ __forceinline__ float lane4(const float4 &v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
-
-__device__ __forceinline__ void cswap(float &ka, int &va, float &kb, int &vb)
-{
-	const bool sw = kb < ka;
-	const float k = sw ? kb : ka;
-	kb = sw ? ka : kb;
-	ka = k;
-	const int v = sw ? vb : va;
-	vb = sw ? va : vb;
-	va = v;
-}
-
-// Near / far planes of a BVH4 node's boxes for one ray.  By the sign of the inverse direction the
-// slab's entry plane is the low bound (1/d >= 0) or the high one for every box, and fma(b, 1/d, -o/d)
-// is monotone in b, so max(near distances) / min(far distances) are exactly the values of the
-// per-child min / max over both planes — 4 x 6 fewer min / max per visit for six per-lane addresses.
-struct SlabSel { int nx, ny, nz; };   // float4 index in the node of the near plane per axis (far: ^ 1)
-__device__ __forceinline__ SlabSel slabSel(V3 id) { return SlabSel{id.x >= 0.f ? 0 : 1, id.y >= 0.f ? 2 : 3, id.z >= 0.f ? 4 : 5}; }
-
-// Child order after a BVH4 visit (results never depend on it: closest hits tie-break on the primitive
-// index, any hits answer occluded / not): closest rays sort the hit inner children by entry distance
-// (YAF_CLOSEST_SORT, the culling order); any-hit rays skip the network (YAF_ANY_SORT=1 restores it)
-#ifndef YAF_ANY_SORT
-#define YAF_ANY_SORT 0
-#endif
-#ifndef YAF_CLOSEST_SORT
-#define YAF_CLOSEST_SORT 1
-#endif
-// BVH4 (bvh.cc: collapsed binary SAH tree, 128 B nodes with the four child boxes in SoA form).
-// Same hit semantics as traverse2: leaf children are tested as soon as their box is hit, inner
-// children are sorted by entry distance (5-exchange network) and descended nearest-first.
-// PACK (LDS-resident trees, < 512 nodes): the closest rays' child order from packed integer keys (below);
-// -DYAF_PACKED_SORT=1 also packs the BVH8 refill loop's 19-exchange network.  Measured and off (r06, same
-// box A/B): C2 k_trace 25.9 -> 27.2 ms per frame (fewer VALU per exchange, but the key packing and the
-// child masks cost more than the selects they replace at the 64-VGPR budget), C4 unchanged (126.4 ms)
-#ifndef YAF_PACKED_SORT
-#define YAF_PACKED_SORT 0
-#endif
-constexpr uint32_t kPackNodeBits = 9;   // node index bits of a packed key: LDS-resident BVH4s have <= 384 nodes (48 KB)
-template<bool ANY, bool SPILL, bool TS = false, bool STATS = true, bool PACK = false>
-__device__ bool traverse4(const TraceCtx &C, V3 o, V3 d, float tmin, float tmax, float &t_best, int &prim_best,
-                          uint32_t &visits, uint32_t &tests, TsList *ts = nullptr)
-{
-#if YAF_LANE_REMAT
-	// the lane's stack column from the wave's first thread (scalar) and the lane id (v_mbcnt, re-derived at
-	// every push / pop — opaque, so not hoisted): at the 64-VGPR budget a loop-invariant column address
-	// was spilled and reloaded from scratch at every push (a vector-memory wait per push)
-#define YAF_LANE ((int)tidFrom(C.wave_base))
-#else
-	const int lane = threadIdx.x;
-#define YAF_LANE lane
-#endif
-	V3 dd = d;
-	if(fabsf(dd.x) < 1e-20f) dd.x = copysignf(1e-20f, dd.x);
-	if(fabsf(dd.y) < 1e-20f) dd.y = copysignf(1e-20f, dd.y);
-	if(fabsf(dd.z) < 1e-20f) dd.z = copysignf(1e-20f, dd.z);
-	const V3 id = v3(rcpExact(dd.x), rcpExact(dd.y), rcpExact(dd.z));
-	// slab distances as fma(bound, 1/d, -o/d): the rounding of o/d is covered by the boxes' build-time
-	// padding (mag * 1e-5, bvh.cc padBox) as the rounding of (bound - o) is
-	const V3 oid = v3(o.x * id.x, o.y * id.y, o.z * id.z);
-	const SlabSel sel = slabSel(id);
-	const float box_t0 = ANY ? -1e-3f : (tmin - 1e-3f * (1.f + fabsf(tmin)));
-	const float inf = __builtin_huge_valf();
-	const uint32_t glane = blockIdx.x * blockDim.x + threadIdx.x;
-	t_best = tmax;
-	prim_best = -1;
-	int sp = 0;
-	int node = 0;
-	// the first lds_depth levels live in LDS; deeper ones (rare) spill to this lane's HBM column
-	auto push = [&](int v) {
-		if(!SPILL || sp < C.lds_depth) C.stack[sp * kTraceBlock + YAF_LANE] = v;   // (!SPILL: the bound fits the LDS levels)
-		else if(SPILL) C.spill[(uint32_t)(sp - C.lds_depth) * C.spill_stride + glane] = v;
-	};
-	// the box culling distance: recomputed only where t_best changes (a closest hit), not per visit
-	auto slackOf = [](float t) { return (t < 3.0e38f) ? t * 1.0000005f + 1e-6f : 3.4e38f; };
-	float slack_t = slackOf(t_best);
-	for(;;)
-	{
-		if(STATS) TRACE_STAT(++visits);
-		const float4 *np = C.nodes + 8 * node;
-		const float4 nx = np[sel.nx], fx = np[sel.nx ^ 1], ny = np[sel.ny], fy = np[sel.ny ^ 1], nz = np[sel.nz], fz = np[sel.nz ^ 1], cf = np[6], kf = np[7];
-		float key[4];
-		int child[4], count[4];
-		uint32_t leaves = 0;
-		// the four slab tests first, so the node's registers are free before any triangle test
-#pragma unroll
-		for(int k = 0; k < 4; ++k)
-		{
-			const float lo = fmaxf(fmaxf(__builtin_fmaf(lane4(nx, k), id.x, -oid.x), __builtin_fmaf(lane4(ny, k), id.y, -oid.y)),
-			                       fmaxf(__builtin_fmaf(lane4(nz, k), id.z, -oid.z), box_t0));
-			const float hi = fminf(fminf(__builtin_fmaf(lane4(fx, k), id.x, -oid.x), __builtin_fmaf(lane4(fy, k), id.y, -oid.y)),
-			                       fminf(__builtin_fmaf(lane4(fz, k), id.z, -oid.z), slack_t));
-			// selects, not branches: a lane-varying `if` here costs an exec-mask save / restore per child
-			const uint32_t h = lo <= hi ? 1u : 0u;
-			child[k] = __float_as_int(lane4(cf, k));
-			count[k] = __float_as_int(lane4(kf, k));
-			const uint32_t inner = child[k] >= 0 ? 1u : 0u;
-			key[k] = (h & inner) ? lo : inf;
-			leaves |= (h & (inner ^ 1u) & (count[k] > 0 ? 1u : 0u)) << k;
-		}
-		// the hit leaves' triangles as one per-lane list (leaf order, then triangle order), so that a
-		// wave runs max-over-lanes tests per node instead of one pass per leaf slot any lane hit
-		int e[4], s4[4];
-		{
-			int acc = 0;
-#pragma unroll
-			for(int k = 0; k < 4; ++k)
-			{
-				const bool l = leaves & (1u << k);
-				s4[k] = ~child[k] - acc;
-				acc += l ? count[k] : 0;
-				e[k] = acc;
-			}
-		}
-		for(int i = 0; i < e[3]; ++i)
-		{
-			const int q = i + (i < e[0] ? s4[0] : i < e[1] ? s4[1] : i < e[2] ? s4[2] : s4[3]);
-			{
-				if(STATS) TRACE_STAT(++tests);
-				const float4 *tp = C.tris + 3 * q;
-				const float4 ta = tp[0], tb = tp[1], tc = tp[2];
-				const float t = triTest(ta, tb, tc, o, d, ANY ? tmax : t_best);
-				if(t == -1.f) continue;
-				const int prim = __float_as_int(tb.w);
-				if(ANY && TS)
-				{
-					// intersectTs: t in [tmin, t_max) of the moved ray (tmin kept, accelerator.cc:82-85)
-					if(t < tmax && t >= tmin && tsShadows(*ts, t, prim)) { t_best = t; prim_best = prim; return true; }
-				}
-				else if(ANY)
-				{
-					if(t < tmax && t >= 0.f) { t_best = t; prim_best = prim; return true; }
-				}
-				else if(t >= tmin && (t < t_best || (t == t_best && prim_best >= 0 && prim < prim_best)))
-				{
-					t_best = t;
-					prim_best = prim;
-					slack_t = slackOf(t_best);
-				}
-			}
-		}
-		int next;
-		if constexpr(ANY && !YAF_ANY_SORT)
-		{
-			// any hit: the answer does not depend on the order the hit children are visited in (there is
-			// no distance to cull against), so no sorting network — the first hit inner child is descended,
-			// the others pushed in node order
-			next = -1;
-#pragma unroll
-			for(int k = 0; k < 4; ++k)
-			{
-				if(!(key[k] < inf)) continue;
-				if(next < 0) next = child[k];
-				else { push(child[k]); ++sp; }
-			}
-		}
-		else if constexpr(PACK && YAF_PACKED_SORT && YAF_CLOSEST_SORT)
-		{
-			// one 32-bit key per hit inner child: the entry distance clamped at 0 with the child's node index in
-			// the low kPackNodeBits bits (the order is a culling heuristic only — closest hits tie-break on the
-			// primitive index, so neither the clamp nor the dropped mantissa bits change a result), sorted as
-			// unsigned integers: a compare-exchange is one v_min_u32 + v_max_u32 instead of a compare and four
-			// selects, and the child comes back with a mask; a missed child is all ones
-			constexpr uint32_t nm = (1u << kPackNodeBits) - 1u;
-			uint32_t pk[4];
-#pragma unroll
-			for(int k = 0; k < 4; ++k)
-				pk[k] = key[k] < inf ? ((__float_as_uint(fmaxf(key[k], 0.f)) & ~nm) | (uint32_t)child[k]) : 0xffffffffu;
-			auto cx = [](uint32_t &a, uint32_t &b) {
-				const uint32_t lo = min(a, b);
-				b = max(a, b);
-				a = lo;
-			};
-			cx(pk[0], pk[1]);
-			cx(pk[2], pk[3]);
-			cx(pk[0], pk[2]);
-			cx(pk[1], pk[3]);
-			cx(pk[1], pk[2]);
-			if(pk[3] != 0xffffffffu) { push((int)(pk[3] & nm)); ++sp; }
-			if(pk[2] != 0xffffffffu) { push((int)(pk[2] & nm)); ++sp; }
-			if(pk[1] != 0xffffffffu) { push((int)(pk[1] & nm)); ++sp; }
-			next = pk[0] != 0xffffffffu ? (int)(pk[0] & nm) : -1;
-		}
-		else if constexpr(!YAF_CLOSEST_SORT)
-		{
-			// (tuning variant) the nearest hit child descended, the others pushed in node order
-			int kmin = 0;
-#pragma unroll
-			for(int k = 1; k < 4; ++k) kmin = key[k] < key[kmin] ? k : kmin;
-			next = key[kmin] < inf ? child[kmin] : -1;
-#pragma unroll
-			for(int k = 3; k >= 0; --k)
-				if(k != kmin && key[k] < inf) { push(child[k]); ++sp; }
-		}
-		else
-		{
-			cswap(key[0], child[0], key[1], child[1]);
-			cswap(key[2], child[2], key[3], child[3]);
-			cswap(key[0], child[0], key[2], child[2]);
-			cswap(key[1], child[1], key[3], child[3]);
-			cswap(key[1], child[1], key[2], child[2]);
-			if(key[3] < inf) { push(child[3]); ++sp; }
-			if(key[2] < inf) { push(child[2]); ++sp; }
-			if(key[1] < inf) { push(child[1]); ++sp; }
-			next = key[0] < inf ? child[0] : -1;
-		}
-		if(next < 0)
-		{
-			if(sp == 0) break;
-			--sp;
-			next = (!SPILL || sp < C.lds_depth) ? C.stack[sp * kTraceBlock + YAF_LANE]
-			                                    : C.spill[(uint32_t)(sp - C.lds_depth) * C.spill_stride + glane];
-		}
-		node = next;
-	}
-	return prim_best >= 0;
-}
-
-// traverse4 with the leaf triangle tests deferred (LDS-resident BVH4, no spill column, opaque shadows;
-// DevQueues::trace_defer).  traverse4 tests a hit leaf's triangles inside the visit, so a wave pays the
-// largest per-lane triangle count of every visit; here a visit only records its hit leaves in the lane's
-// list (LDS, [slot][lane], one 16-bit entry per leaf: first triangle slot in the low kDeferStartBits bits,
-// triangle count above), and the recorded triangles are tested afterwards in one dense loop per lane:
-//   phase 1: visits as in traverse4 (slab tests, box_t0, slack_t, child order, stack) while the lane is
-//            still traversing and its list has room for the four leaves a visit can add;
-//   phase 2: the lane's pending triangles through triTest and traverse4's hit predicates; an any-hit ray
-//            ends at its first hit, a closest hit tightens slack_t for the visits after a flush.
-// A lane leaves phase 1 because its own traversal ended or its own list is full, never because of a
-// neighbour, so a ray's visits and tests are a function of the ray and the capacity alone (the statistics
-// do not depend on how the waves are composed).  Box culling sees t_best only after a flush — a ray visits
-// a superset of traverse4's nodes — and the result is the same: closest hits are the minimum over
-// (t, primitive) of the tested triangles, any hits a boolean.
-constexpr int kDeferStartBits = 10;                      // scenes of < 1024 triangles (an LDS-resident scene holds <= 1024: 48 KB)
-constexpr int kDeferMaxLeaf = (1 << (16 - kDeferStartBits)) - 1;
-constexpr int kDeferRoom = 4;                            // free entries a visit needs (= the smallest capacity)
-template<bool ANY, bool STATS>
-__device__ bool traverse4Defer(const TraceCtx &C, uint16_t *list, int cap, V3 o, V3 d, float tmin, float tmax, float &t_best,
-                               int &prim_best, uint32_t &visits, uint32_t &tests)
-{
-#if !YAF_LANE_REMAT
-	const int lane = threadIdx.x;
-#endif
-	V3 dd = d;
-	if(fabsf(dd.x) < 1e-20f) dd.x = copysignf(1e-20f, dd.x);
-	if(fabsf(dd.y) < 1e-20f) dd.y = copysignf(1e-20f, dd.y);
-	if(fabsf(dd.z) < 1e-20f) dd.z = copysignf(1e-20f, dd.z);
-	const V3 id = v3(rcpExact(dd.x), rcpExact(dd.y), rcpExact(dd.z));
-	const V3 oid = v3(o.x * id.x, o.y * id.y, o.z * id.z);
-	const SlabSel sel = slabSel(id);
-	const float box_t0 = ANY ? -1e-3f : (tmin - 1e-3f * (1.f + fabsf(tmin)));
-	const float inf = __builtin_huge_valf();
-	t_best = tmax;
-	prim_best = -1;
-	int sp = 0;
-	int node = 0;   // -1: the traversal has ended
-	int n = 0;      // pending list entries
-	auto push = [&](int v) { C.stack[sp * kTraceBlock + YAF_LANE] = v; };
-	auto slackOf = [](float t) { return (t < 3.0e38f) ? t * 1.0000005f + 1e-6f : 3.4e38f; };
-	float slack_t = slackOf(t_best);
-	for(;;)
-	{
-		// ---- phase 1: box traversal, hit leaves recorded ----
-		while(node >= 0 && n + kDeferRoom <= cap)
-		{
-			if(STATS) TRACE_STAT(++visits);
-			const float4 *np = C.nodes + 8 * node;
-			const float4 nx = np[sel.nx], fx = np[sel.nx ^ 1], ny = np[sel.ny], fy = np[sel.ny ^ 1], nz = np[sel.nz], fz = np[sel.nz ^ 1], cf = np[6], kf = np[7];
-			float key[4];
-			int child[4];
-			uint16_t *lp = list + n * kTraceBlock + YAF_LANE;
-#pragma unroll
-			for(int k = 0; k < 4; ++k)
-			{
-				const float lo = fmaxf(fmaxf(__builtin_fmaf(lane4(nx, k), id.x, -oid.x), __builtin_fmaf(lane4(ny, k), id.y, -oid.y)),
-				                       fmaxf(__builtin_fmaf(lane4(nz, k), id.z, -oid.z), box_t0));
-				const float hi = fminf(fminf(__builtin_fmaf(lane4(fx, k), id.x, -oid.x), __builtin_fmaf(lane4(fy, k), id.y, -oid.y)),
-				                       fminf(__builtin_fmaf(lane4(fz, k), id.z, -oid.z), slack_t));
-				const uint32_t h = lo <= hi ? 1u : 0u;
-				child[k] = __float_as_int(lane4(cf, k));
-				const int count = __float_as_int(lane4(kf, k));
-				const uint32_t inner = child[k] >= 0 ? 1u : 0u;
-				key[k] = (h & inner) ? lo : inf;
-				// every child's entry is stored at the lane's next slot and kept only where the child is a hit
-				// leaf (the slot then advances; n + 4 <= cap holds on entry): no lane-varying branch per child
-				const uint32_t leaf = h & (inner ^ 1u) & (count > 0 ? 1u : 0u);
-				*lp = (uint16_t)((uint32_t)~child[k] | ((uint32_t)count << kDeferStartBits));
-				lp += leaf ? kTraceBlock : 0;
-				n += (int)leaf;
-			}
-			int next;
-			if constexpr(ANY && !YAF_ANY_SORT)
-			{
-				next = -1;
-#pragma unroll
-				for(int k = 0; k < 4; ++k)
-				{
-					if(!(key[k] < inf)) continue;
-					if(next < 0) next = child[k];
-					else { push(child[k]); ++sp; }
-				}
-			}
-			else
-			{
-				cswap(key[0], child[0], key[1], child[1]);
-				cswap(key[2], child[2], key[3], child[3]);
-				cswap(key[0], child[0], key[2], child[2]);
-				cswap(key[1], child[1], key[3], child[3]);
-				cswap(key[1], child[1], key[2], child[2]);
-				if(key[3] < inf) { push(child[3]); ++sp; }
-				if(key[2] < inf) { push(child[2]); ++sp; }
-				if(key[1] < inf) { push(child[1]); ++sp; }
-				next = key[0] < inf ? child[0] : -1;
-			}
-			if(next < 0 && sp > 0)
-			{
-				--sp;
-				next = C.stack[sp * kTraceBlock + YAF_LANE];
-			}
-			node = next;
-		}
-		// ---- phase 2: the pending leaves' triangles, one per trip whatever leaf they belong to ----
-		// (last recorded leaf first: n is the loop's only index, and no result depends on the order)
-		uint32_t ent = 0;   // the leaf being tested: next triangle slot | triangles left << kDeferStartBits
-		for(;;)
-		{
-			if((ent >> kDeferStartBits) == 0)
-			{
-				if(n == 0) break;
-				--n;
-				ent = list[n * kTraceBlock + YAF_LANE];
-			}
-			if(STATS) TRACE_STAT(++tests);
-			const float4 *tp = C.tris + 3 * (ent & ((1u << kDeferStartBits) - 1u));
-			const float4 ta = tp[0], tb = tp[1], tc = tp[2];
-			ent += 1u - (1u << kDeferStartBits);   // (the slot of a leaf's last triangle + 1 <= 1023: no carry into the count)
-			const float t = triTest(ta, tb, tc, o, d, ANY ? tmax : t_best);
-			if(t == -1.f) continue;
-			const int prim = __float_as_int(tb.w);
-			if(ANY)
-			{
-				if(t < tmax && t >= 0.f) { t_best = t; prim_best = prim; node = -1; break; }
-			}
-			else if(t >= tmin && (t < t_best || (t == t_best && prim_best >= 0 && prim < prim_best)))
-			{
-				t_best = t;
-				prim_best = prim;
-				slack_t = slackOf(t_best);
-			}
-		}
-		n = 0;
-		if(node < 0) break;
-	}
-	return prim_best >= 0;
-}
-
-// k_trace's BVH4 loop with per-lane ray refill: a lane works through its own sequence of queue
-// entries (j, j + stride, ...), closest rays then shadow rays, and starts its next ray as soon as
-// its traversal ends, so a wave runs as long as its longest lane's sum of rays instead of the sum
-// over rays of the longest lane.  Every ray runs the sequence of traverse4 (same visits, culling,
-// leaf order and early exits), so hits are identical.
-#undef YAF_LANE
-
-template<bool SPILL, bool STATS = true>
-__device__ void traceRefill4(const TraceCtx &C, const DevQueues &Q, const DevPaths &P, uint32_t n_a, uint32_t total,
-                             uint32_t a0, uint32_t s0, uint32_t j, uint32_t stride, uint32_t &visits, uint32_t &tests,
-                             uint32_t &n_closest, uint32_t &n_shadow)
-{
-	const int lane = threadIdx.x;
-	const uint32_t glane = blockIdx.x * blockDim.x + threadIdx.x;
-	const float inf = __builtin_huge_valf();
-	V3 o = v3(0.f, 0.f, 0.f), d = o, id = o, oid = o;
-	SlabSel sel{0, 2, 4};
-	float tmin = 0.f, tmax = 0.f, box_t0 = 0.f, t_best = 0.f;
-	int prim_best = -1, sp = 0, node = -1;
-	bool any = false;
-	uint32_t cur = 0;
-	auto push = [&](int v) {
-		if(sp < C.lds_depth) C.stack[sp * kTraceBlock + lane] = v;
-		else if(SPILL) C.spill[(uint32_t)(sp - C.lds_depth) * C.spill_stride + glane] = v;
-	};
-	for(;;)
-	{
-		if(node < 0)
-		{
-			// next ray of this lane (closest entries with a NaN direction carry no ray)
-			bool got = false;
-			for(;;)
-			{
-				if(j >= total) break;
-				cur = j;
-				j += stride;
-				if(cur < n_a)
-				{
-					float tw;
-					if(!loadQRay(Q, a0 + cur, o, d, tmin, tw)) continue;
-					tmax = (tw >= 0.f) ? tw : inf;
-					any = false;
-					++n_closest;
-				}
-				else
-				{
-					const float4 od = rayLd4(&Q.sh_o[s0 + (cur - n_a)]);
-					const float4 dd = rayLd4(&Q.sh_d[s0 + (cur - n_a)]);
-					o = xyz(od);
-					d = xyz(dd);
-					tmin = 0.f;
-					tmax = dd.w;
-					any = true;
-					++n_shadow;
-				}
-				got = true;
-				break;
-			}
-			if(!got) break;
-			V3 dq = d;
-			if(fabsf(dq.x) < 1e-20f) dq.x = copysignf(1e-20f, dq.x);
-			if(fabsf(dq.y) < 1e-20f) dq.y = copysignf(1e-20f, dq.y);
-			if(fabsf(dq.z) < 1e-20f) dq.z = copysignf(1e-20f, dq.z);
-			id = v3(rcpExact(dq.x), rcpExact(dq.y), rcpExact(dq.z));
-			oid = v3(o.x * id.x, o.y * id.y, o.z * id.z);
-			sel = slabSel(id);
-			box_t0 = any ? -1e-3f : (tmin - 1e-3f * (1.f + fabsf(tmin)));
-			t_best = tmax;
-			prim_best = -1;
-			sp = 0;
-			node = 0;
-		}
-		if(STATS) TRACE_STAT(++visits);
-		float4 nx, fx, ny, fy, nz, fz, cf, kf;
-		if(node < C.n_top)
-		{
-			// the top treelet from LDS (an explicit LDS pointer: ds_read, not flat loads)
-			typedef float V4 __attribute__((ext_vector_type(4)));
-			typedef const __attribute__((address_space(3))) V4 *LdsV4;
-			const LdsV4 tp = (LdsV4)(C.top + kTopStride * node);
-			auto ld = [&](int k) {
-				const V4 v = tp[k];
-				return make_float4(v.x, v.y, v.z, v.w);
-			};
-			nx = ld(sel.nx); fx = ld(sel.nx ^ 1); ny = ld(sel.ny); fy = ld(sel.ny ^ 1); nz = ld(sel.nz); fz = ld(sel.nz ^ 1); cf = ld(6); kf = ld(7);
-		}
-		else
-		{
-			const float4 *np = C.nodes + 8 * node;
-			nx = np[sel.nx]; fx = np[sel.nx ^ 1]; ny = np[sel.ny]; fy = np[sel.ny ^ 1]; nz = np[sel.nz]; fz = np[sel.nz ^ 1]; cf = np[6]; kf = np[7];
-		}
-		const float slack_t = (t_best < 3.0e38f) ? t_best * 1.0000005f + 1e-6f : 3.4e38f;
-		float key[4];
-		int child[4], e[4], s4[4];
-		int acc = 0;
-#pragma unroll
-		for(int k = 0; k < 4; ++k)
-		{
-			const float lo = fmaxf(fmaxf(__builtin_fmaf(lane4(nx, k), id.x, -oid.x), __builtin_fmaf(lane4(ny, k), id.y, -oid.y)),
-			                       fmaxf(__builtin_fmaf(lane4(nz, k), id.z, -oid.z), box_t0));
-			const float hi = fminf(fminf(__builtin_fmaf(lane4(fx, k), id.x, -oid.x), __builtin_fmaf(lane4(fy, k), id.y, -oid.y)),
-			                       fminf(__builtin_fmaf(lane4(fz, k), id.z, -oid.z), slack_t));
-			const uint32_t h = lo <= hi ? 1u : 0u;
-			child[k] = __float_as_int(lane4(cf, k));
-			const int count = __float_as_int(lane4(kf, k));
-			const uint32_t inner = child[k] >= 0 ? 1u : 0u;
-			key[k] = (h & inner) ? lo : inf;
-			s4[k] = ~child[k] - acc;
-			acc += (h & (inner ^ 1u)) ? count : 0;
-			e[k] = acc;
-		}
-		bool done = false;
-		for(int i = 0; i < e[3]; ++i)
-		{
-			const int q = i + (i < e[0] ? s4[0] : i < e[1] ? s4[1] : i < e[2] ? s4[2] : s4[3]);
-			if(STATS) TRACE_STAT(++tests);
-			const float4 *tp = C.tris + 3 * q;
-			const float4 ta = tp[0], tb = tp[1], tc = tp[2];
-			const float t = triTest(ta, tb, tc, o, d, t_best);
-			if(t == -1.f) continue;
-			const int prim = __float_as_int(tb.w);
-			if(any)
-			{
-				if(t < tmax && t >= 0.f) { t_best = t; prim_best = prim; done = true; break; }
-			}
-			else if(t >= tmin && (t < t_best || (t == t_best && prim_best >= 0 && prim < prim_best)))
-			{
-				t_best = t;
-				prim_best = prim;
-			}
-		}
-		if(!done)
-		{
-			cswap(key[0], child[0], key[1], child[1]);
-			cswap(key[2], child[2], key[3], child[3]);
-			cswap(key[0], child[0], key[2], child[2]);
-			cswap(key[1], child[1], key[3], child[3]);
-			cswap(key[1], child[1], key[2], child[2]);
-			if(key[3] < inf) { push(child[3]); ++sp; }
-			if(key[2] < inf) { push(child[2]); ++sp; }
-			if(key[1] < inf) { push(child[1]); ++sp; }
-			int next = key[0] < inf ? child[0] : -1;
-			if(next < 0 && sp > 0)
-			{
-				--sp;
-				next = (!SPILL || sp < C.lds_depth) ? C.stack[sp * kTraceBlock + lane]
-				                                    : C.spill[(uint32_t)(sp - C.lds_depth) * C.spill_stride + glane];
-			}
-			node = next;
-			done = next < 0;
-		}
-		if(done)
-		{
-			// (the NEE entry of an opaque shadow ray rides in sh_o.w: re-read at the end rather than held
-			// in a register through the traversal, which spilled at this kernel's 6-wave budget)
-			if(any) P.occ[__float_as_int(Q.sh_o[s0 + (cur - n_a)].w)] = prim_best >= 0 ? 1 : 0;   // P = state set of the consumer shade
-			else
-			{
-				raySt(&Q.hit_t[a0 + cur], t_best);
-				raySt(&Q.hit_prim[a0 + cur], prim_best);
-			}
-			node = -1;
-		}
-	}
-}
-
-// ---- quantised BVH8 (bvhgpu.hip k_q8_write: the device-built tree collapsed to eight children, child
-// boxes as bytes over a per-node origin and power-of-two quanta, rounded outwards; opt-in for scenes in
-// global memory).  A visit reads 80 B (one line): origin, quanta, child masks, the first inner child, the
-// first leaf triangle (the BVH8's own triangle array, leaves in node order) and the six byte planes;
-// the slab test decodes t = q · (2^e / d) + (origin − o) / d.  The decoded boxes contain the float boxes
-// (which carry the BVH4's padding), the triangle test and the tie rule are the BVH4's: the same hits.
-#ifndef YAF_W8_SORT
-#define YAF_W8_SORT 1
-#endif
-constexpr int kTop8Stride = 5;   // float4 per staged node in LDS (the 80 B a visit reads: 20 dwords, so 16
-                                 // consecutive nodes start on 16 distinct bank quads)
-__device__ __forceinline__ float q8Byte(uint32_t lo4, uint32_t hi4, int k)
-{
-	const uint32_t w = k < 4 ? lo4 : hi4;
-	return (float)((w >> (8 * (k & 3))) & 0xffu);   // (v_cvt_f32_ubyteN)
-}
-
-template<bool SPILL, bool STATS = true>
-__device__ void traceRefill8(const TraceCtx &C, const DevQueues &Q, const DevPaths &P, uint32_t n_a, uint32_t total,
-                             uint32_t a0, uint32_t s0, uint32_t j, uint32_t stride, uint32_t &visits, uint32_t &tests,
-                             uint32_t &n_closest, uint32_t &n_shadow)
-{
-	const uint32_t glane = blockIdx.x * blockDim.x + threadIdx.x;
-	const float inf = __builtin_huge_valf();
-	V3 o = v3(0.f, 0.f, 0.f), d = o, id = o;
-	float tmin = 0.f, tmax = 0.f, box_t0 = 0.f, t_best = 0.f;
-	int prim_best = -1, sp = 0, node = -1;
-	bool any = false;
-	uint32_t cur = 0;
-	auto push = [&](int v) {
-		if(sp < C.lds_depth) C.stack[sp * kTraceBlock + (int)tidFrom(C.wave_base)] = v;
-		else if(SPILL) C.spill[(uint32_t)(sp - C.lds_depth) * C.spill_stride + glane] = v;
-	};
-	for(;;)
-	{
-		if(node < 0)
-		{
-			bool got = false;
-			for(;;)
-			{
-				if(j >= total) break;
-				cur = j;
-				j += stride;
-				if(cur < n_a)
-				{
-					float tw;
-					// (ray binning: the entry's ray and hit live at the permuted queue address)
-					if(Q.perm) cur = Q.perm[a0 + cur] - a0;
-					if(!loadQRay(Q, a0 + cur, o, d, tmin, tw)) continue;
-					tmax = (tw >= 0.f) ? tw : inf;
-					any = false;
-					++n_closest;
-				}
-				else
-				{
-					const float4 od = rayLd4(&Q.sh_o[s0 + (cur - n_a)]);
-					const float4 dd = rayLd4(&Q.sh_d[s0 + (cur - n_a)]);
-					o = xyz(od);
-					d = xyz(dd);
-					tmin = 0.f;
-					tmax = dd.w;
-					any = true;
-					++n_shadow;
-				}
-				got = true;
-				break;
-			}
-			if(!got) break;
-			V3 dq = d;
-			if(fabsf(dq.x) < 1e-20f) dq.x = copysignf(1e-20f, dq.x);
-			if(fabsf(dq.y) < 1e-20f) dq.y = copysignf(1e-20f, dq.y);
-			if(fabsf(dq.z) < 1e-20f) dq.z = copysignf(1e-20f, dq.z);
-			id = v3(rcpExact(dq.x), rcpExact(dq.y), rcpExact(dq.z));
-			box_t0 = any ? -1e-3f : (tmin - 1e-3f * (1.f + fabsf(tmin)));
-			t_best = tmax;
-			prim_best = -1;
-			sp = 0;
-			node = 0;
-		}
-		if(STATS) TRACE_STAT(++visits);
-		float4 n0, n1, n2, n3, n4;
-		if(node < C.n_top)
-		{
-			typedef float V4 __attribute__((ext_vector_type(4)));
-			typedef const __attribute__((address_space(3))) V4 *LdsV4;
-			const LdsV4 tp = (LdsV4)(C.top + kTop8Stride * node);
-			auto ld = [&](int k) {
-				const V4 v = tp[k];
-				return make_float4(v.x, v.y, v.z, v.w);
-			};
-			n0 = ld(0); n1 = ld(1); n2 = ld(2); n3 = ld(3); n4 = ld(4);
-		}
-		else
-		{
-			const float4 *np = C.nodes + 8 * node;
-			n0 = np[0]; n1 = np[1]; n2 = np[2]; n3 = np[3]; n4 = np[4];
-		}
-		const uint32_t meta = __float_as_uint(n0.w);
-		const uint32_t inner = meta >> 24, leaf = __float_as_uint(n1.x) & 0xffu;
-		const int inner_base = __float_as_int(n1.y), tri_base = __float_as_int(n1.z);
-		// per axis: t of plane q = q * A + B (A = 2^e / d, B = (origin - o) / d), near / far byte rows by the sign of 1/d
-		const float ax = __uint_as_float((meta & 0xffu) << 23) * id.x, ay = __uint_as_float(((meta >> 8) & 0xffu) << 23) * id.y,
-		            az = __uint_as_float(((meta >> 16) & 0xffu) << 23) * id.z;
-		const float bx = (n0.x - o.x) * id.x, by = (n0.y - o.y) * id.y, bz = (n0.z - o.z) * id.z;
-		const bool px = id.x >= 0.f, py = id.y >= 0.f, pz = id.z >= 0.f;
-		const uint32_t nx0 = __float_as_uint(px ? n2.x : n2.z), nx1 = __float_as_uint(px ? n2.y : n2.w);
-		const uint32_t fx0 = __float_as_uint(px ? n2.z : n2.x), fx1 = __float_as_uint(px ? n2.w : n2.y);
-		const uint32_t ny0 = __float_as_uint(py ? n3.x : n3.z), ny1 = __float_as_uint(py ? n3.y : n3.w);
-		const uint32_t fy0 = __float_as_uint(py ? n3.z : n3.x), fy1 = __float_as_uint(py ? n3.w : n3.y);
-		const uint32_t nz0 = __float_as_uint(pz ? n4.x : n4.z), nz1 = __float_as_uint(pz ? n4.y : n4.w);
-		const uint32_t fz0 = __float_as_uint(pz ? n4.z : n4.x), fz1 = __float_as_uint(pz ? n4.w : n4.y);
-		const float slack_t = (t_best < 3.0e38f) ? t_best * 1.0000005f + 1e-6f : 3.4e38f;
-		float key[8];
-		int child[8];
-		uint32_t leaves = 0;
-#pragma unroll
-		for(int k = 0; k < 8; ++k)
-		{
-			const float lo = fmaxf(fmaxf(__builtin_fmaf(q8Byte(nx0, nx1, k), ax, bx), __builtin_fmaf(q8Byte(ny0, ny1, k), ay, by)),
-			                       fmaxf(__builtin_fmaf(q8Byte(nz0, nz1, k), az, bz), box_t0));
-			const float hi = fminf(fminf(__builtin_fmaf(q8Byte(fx0, fx1, k), ax, bx), __builtin_fmaf(q8Byte(fy0, fy1, k), ay, by)),
-			                       fminf(__builtin_fmaf(q8Byte(fz0, fz1, k), az, bz), slack_t));
-			const uint32_t h = lo <= hi ? 1u : 0u;
-			const uint32_t isi = (inner >> k) & 1u;
-			key[k] = (h & isi) ? lo : inf;
-			child[k] = inner_base + __builtin_popcount(inner & ((1u << k) - 1u));
-			leaves |= (h & (leaf >> k) & 1u) << k;
-		}
-		bool done = false;
-		for(uint32_t m = leaves; m; m &= m - 1u)
-		{
-			const int k = __builtin_ctz(m);
-			const int q = tri_base + __builtin_popcount(leaf & ((1u << k) - 1u));
-			if(STATS) TRACE_STAT(++tests);
-			const float4 *tp = C.tris + 3 * q;
-			const float4 ta = tp[0], tb = tp[1], tc = tp[2];
-			const float t = triTest(ta, tb, tc, o, d, t_best);
-			if(t == -1.f) continue;
-			const int prim = __float_as_int(tb.w);
-			if(any)
-			{
-				if(t < tmax && t >= 0.f) { t_best = t; prim_best = prim; done = true; break; }
-			}
-			else if(t >= tmin && (t < t_best || (t == t_best && prim_best >= 0 && prim < prim_best)))
-			{
-				t_best = t;
-				prim_best = prim;
-			}
-		}
-		if(!done && YAF_W8_SORT && YAF_PACKED_SORT)
-		{
-			// the same network over packed 32-bit keys: the entry distance clamped at 0 with the child's rank
-			// among the node's inner children (consecutive from inner_base) in the low 3 bits, compared as
-			// unsigned integers (v_min_u32 + v_max_u32 per exchange instead of a compare and four selects; no
-			// child array).  The order is a culling heuristic only: closest hits tie-break on the primitive
-			// index and any-hit rays answer occluded or not, so the clamp and the 3 dropped mantissa bits
-			// change no result.  A missed child is all ones.
-			uint32_t pk[8];
-#pragma unroll
-			for(int k = 0; k < 8; ++k)
-				pk[k] = key[k] < inf ? ((__float_as_uint(fmaxf(key[k], 0.f)) & ~7u) | (uint32_t)__builtin_popcount(inner & ((1u << k) - 1u)))
-				                     : 0xffffffffu;
-			auto cx = [](uint32_t &a, uint32_t &b) {
-				const uint32_t lo = min(a, b);
-				b = max(a, b);
-				a = lo;
-			};
-			cx(pk[0], pk[1]); cx(pk[2], pk[3]); cx(pk[4], pk[5]); cx(pk[6], pk[7]);
-			cx(pk[0], pk[2]); cx(pk[1], pk[3]); cx(pk[4], pk[6]); cx(pk[5], pk[7]);
-			cx(pk[1], pk[2]); cx(pk[5], pk[6]);
-			cx(pk[0], pk[4]); cx(pk[1], pk[5]); cx(pk[2], pk[6]); cx(pk[3], pk[7]);
-			cx(pk[2], pk[4]); cx(pk[3], pk[5]);
-			cx(pk[1], pk[2]); cx(pk[3], pk[4]); cx(pk[5], pk[6]);
-#pragma unroll
-			for(int k = 7; k >= 1; --k)
-				if(pk[k] != 0xffffffffu) { push(inner_base + (int)(pk[k] & 7u)); ++sp; }
-			int next = pk[0] != 0xffffffffu ? inner_base + (int)(pk[0] & 7u) : -1;
-			if(next < 0 && sp > 0)
-			{
-				--sp;
-				next = (!SPILL || sp < C.lds_depth) ? C.stack[sp * kTraceBlock + (int)tidFrom(C.wave_base)]
-				                                    : C.spill[(uint32_t)(sp - C.lds_depth) * C.spill_stride + glane];
-			}
-			node = next;
-			done = next < 0;
-		}
-		else if(!done)
-		{
-			if(YAF_W8_SORT)
-			{
-				// Batcher's odd-even merge network (19 compare-exchanges): nearest child descended first, the
-				// others pushed farthest first
-				cswap(key[0], child[0], key[1], child[1]); cswap(key[2], child[2], key[3], child[3]);
-				cswap(key[4], child[4], key[5], child[5]); cswap(key[6], child[6], key[7], child[7]);
-				cswap(key[0], child[0], key[2], child[2]); cswap(key[1], child[1], key[3], child[3]);
-				cswap(key[4], child[4], key[6], child[6]); cswap(key[5], child[5], key[7], child[7]);
-				cswap(key[1], child[1], key[2], child[2]); cswap(key[5], child[5], key[6], child[6]);
-				cswap(key[0], child[0], key[4], child[4]); cswap(key[1], child[1], key[5], child[5]);
-				cswap(key[2], child[2], key[6], child[6]); cswap(key[3], child[3], key[7], child[7]);
-				cswap(key[2], child[2], key[4], child[4]); cswap(key[3], child[3], key[5], child[5]);
-				cswap(key[1], child[1], key[2], child[2]); cswap(key[3], child[3], key[4], child[4]);
-				cswap(key[5], child[5], key[6], child[6]);
-			}
-			else
-			{
-				int kmin = 0;
-#pragma unroll
-				for(int k = 1; k < 8; ++k) kmin = key[k] < key[kmin] ? k : kmin;
-#pragma unroll
-				for(int k = 1; k < 8; ++k)
-					if(k == kmin) { cswap(key[0], child[0], key[k], child[k]); }
-			}
-#pragma unroll
-			for(int k = 7; k >= 1; --k)
-				if(key[k] < inf) { push(child[k]); ++sp; }
-			int next = key[0] < inf ? child[0] : -1;
-			if(next < 0 && sp > 0)
-			{
-				--sp;
-				next = (!SPILL || sp < C.lds_depth) ? C.stack[sp * kTraceBlock + (int)tidFrom(C.wave_base)]
-				                                    : C.spill[(uint32_t)(sp - C.lds_depth) * C.spill_stride + glane];
-			}
-			node = next;
-			done = next < 0;
-		}
-		if(done)
-		{
-			if(any) P.occ[__float_as_int(Q.sh_o[s0 + (cur - n_a)].w)] = prim_best >= 0 ? 1 : 0;
-			else
-			{
-				raySt(&Q.hit_t[a0 + cur], t_best);
-				raySt(&Q.hit_prim[a0 + cur], prim_best);
-			}
-			node = -1;
-		}
-	}
-}
-
-template<bool ANY, bool WIDE, bool SPILL = true, bool TS = false, bool STATS = true, bool PACK = false>
-__device__ __forceinline__ bool traverse(const TraceCtx &C, V3 o, V3 d, float tmin, float tmax, float &t_best,
-                                         int &prim_best, uint32_t &visits, uint32_t &tests, TsList *ts = nullptr)
-{
-	if(WIDE) return traverse4<ANY, SPILL, TS, STATS, PACK>(C, o, d, tmin, tmax, t_best, prim_best, visits, tests, ts);
-	return traverse2<ANY, TS, STATS>(C, o, d, tmin, tmax, t_best, prim_best, visits, tests, ts);
-}
-
 // k_trace asks the register allocator for 8 waves per SIMD for LDS-resident scenes (<= 64 VGPRs;
 // measured +3% on C2 over the unconstrained 68) and 6 for scenes in global memory, whose refill
 // loop (traceRefill4) needs the registers (C4: 226 -> 189 ms of k_trace per frame at 6, spills at 8);
@@ -1727,7 +685,7 @@ __global__ void __launch_bounds__(kTraceBlock) YAF_TRACE_ATTR k_trace(DevScene S
 				int prim;
 				const float tmax = (tw >= 0.f) ? tw : __builtin_huge_valf();
 				if constexpr(DEFER) traverse4Defer<false, STATS>(C, dlist, Q.trace_defer, o, d, tmin, tmax, t, prim, visits, tests);
-				else traverse<false, WIDE, SPILL, false, STATS, LDS_SCENE>(C, o, d, tmin, tmax, t, prim, visits, tests);
+				else traverse<false, WIDE, SPILL, false, STATS>(C, o, d, tmin, tmax, t, prim, visits, tests);
 				raySt(&Q.hit_t[i], t);
 				raySt(&Q.hit_prim[i], prim);
 				return 1;
@@ -1789,11 +747,6 @@ __global__ void __launch_bounds__(kTraceBlock) YAF_TRACE_ATTR k_trace(DevScene S
 	}
 	else
 	{
-#ifdef YAF_TRACE_NOREFILL
-	// the BVH8 (quantised 80-B nodes, its own triangle order) is only walked by traceRefill8; traceEntry
-	// reads C.nodes as a BVH4
-	static_assert(!W8, "YAF_TRACE_NOREFILL builds cannot traverse the quantised BVH8: set YAFARAY_AMD_BVH8=0 and drop the W8 instantiations");
-#else
 	// refill pays where traversals are long (meshes in global memory: C4 -16%); on the short
 	// LDS-resident traversals of small scenes its per-visit bookkeeping costs more (C2 +35%)
 	if(W8)
@@ -1801,10 +754,9 @@ __global__ void __launch_bounds__(kTraceBlock) YAF_TRACE_ATTR k_trace(DevScene S
 	else if(!LDS_SCENE && WIDE && !TS)
 		traceRefill4<true, STATS>(C, Q, P, n_a, total, a0, s0, L.r * blockDim.x + threadIdx.x, stride, visits, tests, n_closest, n_shadow);
 	else
-#endif
 	// one uniform trip count per workgroup so every lane reaches the same exits (the lane's thread index
 	// re-derived per entry: threadIdx.x kept live across the traversal was spilled and reloaded per visit)
-	for(uint32_t base = j_first + L.r * blockDim.x; base < total; base += stride) countWave(traceEntry(base + (YAF_LANE_REMAT ? tidFrom(C.wave_base) : threadIdx.x)));
+	for(uint32_t base = j_first + L.r * blockDim.x; base < total; base += stride) countWave(traceEntry(base + tidFrom(C.wave_base)));
 	}
 	if(laneId() == 0)
 	{
@@ -1845,42 +797,6 @@ __global__ void __launch_bounds__(kTraceBlock) YAF_TRACE_ATTR k_trace(DevScene S
 // ---------------------------------------------------------------------------------------------
 constexpr int kBruteTris = 64;
 #ifdef YAF_EXPERIMENTS
-
-template<bool ANY>
-__device__ __forceinline__ bool bruteTrace(const float4 *__restrict__ tris, int n_tris, V3 o, V3 d, float tmin, float tmax, float &t_best,
-                                           int &prim_best, uint32_t &tests, bool active)
-{
-	t_best = tmax;
-	prim_best = -1;
-	bool hit = false;
-	for(int q = 0; q < n_tris; ++q)
-	{
-		// wave-uniform index through the constant address space -> scalar loads (the K$ holds the
-		// whole scene)
-#ifdef __HIP_DEVICE_COMPILE__
-		typedef const float4 __attribute__((address_space(4))) *ConstF4;
-		const ConstF4 ct = (ConstF4)tris;
-		const int qs = __builtin_amdgcn_readfirstlane(q);
-		const float4 ta = ct[3 * qs], tb = ct[3 * qs + 1], tc = ct[3 * qs + 2];
-#else   // (host pass of the single-source compile: never executed)
-		const float4 ta = tris[3 * q], tb = tris[3 * q + 1], tc = tris[3 * q + 2];
-#endif
-		const float t = triTest(ta, tb, tc, o, d, t_best);
-		const int prim = __float_as_int(tb.w);
-		if(ANY)
-		{
-			if(!hit && t != -1.f && t < tmax && t >= 0.f) { hit = true; t_best = t; prim_best = prim; }
-			if((q & 3) == 3 && __all(hit || !active)) break;
-		}
-		else if(t != -1.f && t >= tmin && (t < t_best || (t == t_best && prim_best >= 0 && prim < prim_best)))
-		{
-			t_best = t;
-			prim_best = prim;
-		}
-	}
-	if(active) tests += (uint32_t)n_tris;
-	return prim_best >= 0;
-}
 
 __global__ void __launch_bounds__(kTraceBlock) k_trace_brute(DevScene S, DevQueues Q, DevCounters cnt, DevPaths P, DevStats *stats)
 {
@@ -2510,12 +1426,7 @@ __device__ int meshLightClosest(const DevScene &S, const DevLight &L, V3 o, V3 d
 {
 	const float4 *nodes = S.mesh_nodes + 4 * (size_t)L.bvh_node0;
 	const float4 *tris = S.mesh_btris + 3 * (size_t)L.bvh_tri0;
-	V3 dd = d;
-	if(fabsf(dd.x) < 1e-20f) dd.x = copysignf(1e-20f, dd.x);
-	if(fabsf(dd.y) < 1e-20f) dd.y = copysignf(1e-20f, dd.y);
-	if(fabsf(dd.z) < 1e-20f) dd.z = copysignf(1e-20f, dd.z);
-	const V3 id = v3(rcpExact(dd.x), rcpExact(dd.y), rcpExact(dd.z));
-	const float box_t0 = tmin - 1e-3f * (1.f + fabsf(tmin));
+	const RayPrep R = rayPrep(o, d, tmin, false);
 	float t_best = __builtin_huge_valf();
 	int best = -1;
 	int stk[64];
@@ -2524,10 +1435,10 @@ __device__ int meshLightClosest(const DevScene &S, const DevLight &L, V3 o, V3 d
 	{
 		const float4 *np = nodes + 4 * node;
 		const float4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
-		const float slack_t = (t_best < 3.0e38f) ? t_best * 1.0000005f + 1e-6f : 3.4e38f;
+		const float slack_t = slackOf(t_best);
 		bool h0, h1;
 		float tn0, tn1;
-		boxPair(n0, n1, n2, o, id, box_t0, slack_t, h0, h1, tn0, tn1);
+		boxPair(n0, n1, n2, o, R.id, R.box_t0, slack_t, h0, h1, tn0, tn1);
 		const int c0 = __float_as_int(n3.x), c1 = __float_as_int(n3.y), k0 = __float_as_int(n3.z), k1 = __float_as_int(n3.w);
 #pragma unroll
 		for(int side = 0; side < 2; ++side)
@@ -2538,7 +1449,7 @@ __device__ int meshLightClosest(const DevScene &S, const DevLight &L, V3 o, V3 d
 			for(int q = ~c; q < ~c + k; ++q)
 			{
 				const float4 ta = tris[3 * q], tb = tris[3 * q + 1], tc = tris[3 * q + 2];
-				const float t = triTest(ta, tb, tc, o, d, t_best);
+				const float t = triTest(ta, tb, tc, o, d);
 				const int face = __float_as_int(tb.w);
 				if(t != -1.f && t >= tmin && (t < t_best || (t == t_best && face < best)))
 				{
@@ -2589,7 +1500,7 @@ __device__ __forceinline__ bool lightMatHit(const DevScene &S, const DevLight &L
 		else
 			for(int k = 0; k < (int)L.mesh_n; ++k)
 			{
-				const float th = triTest(tr[kMeshTriF4 * k], tr[kMeshTriF4 * k + 1], tr[kMeshTriF4 * k + 2], p, dir, t_best);
+				const float th = triTest(tr[kMeshTriF4 * k], tr[kMeshTriF4 * k + 1], tr[kMeshTriF4 * k + 2], p, dir);
 				if(th != -1.f && th >= b_tmin && th < t_best)
 				{
 					t_best = th;
@@ -3948,147 +2859,6 @@ struct PathShadows
 		}
 	}
 };
-
-// The rays one k_path lane owes before its next vertex: the shadow rays its last NEE recorded
-// (rec entries with `want`, when `shadows`) and its closest ray (when `closest`).  traceRefill4's
-// scheme: one BVH4 visit per loop trip and a lane starts its next ray as soon as one ends, so the
-// wave runs for its busiest lane's sum of traversals (not one full traversal per ray slot, most of
-// whose lanes would idle: the MIS material-sample shadow ray exists for a few lanes only).  Every ray
-// runs traverse4's exact sequence of visits, culling, leaf order and exits: hits are identical.
-template<bool STATS, int STRIDE = kTraceBlock>
-__device__ __forceinline__ void traceLaneRays(const TraceCtx &C, const float4 *rec, uint8_t *occ, int K, bool shadows, bool closest, V3 co,
-                                              V3 cd, float ctmin, float ctmax, float &hit_t, int &hit_prim, uint32_t &visits,
-                                              uint32_t &tests, uint32_t &n_closest, uint32_t &n_shadow)
-{
-	const int lane = threadIdx.x;
-	const float inf = __builtin_huge_valf();
-	V3 o = v3(0.f, 0.f, 0.f), d = o, id = o, oid = o;
-	SlabSel sel{0, 2, 4};
-	float tmax = 0.f, tmin = 0.f, box_t0 = 0.f, t_best = 0.f;
-	int prim_best = -1, sp = 0, node = -1, cur = 0;
-	int e = shadows ? 0 : K;
-	bool any = false, cl = closest;
-	for(;;)
-	{
-		if(node < 0)
-		{
-			// this lane's next ray: the recorded shadow rays in entry order, then the closest ray
-			bool got = false;
-			while(e < K)
-			{
-				const int ee = e++;
-				const float4 dd = rec[2 * ee + 1];
-				if(dd.w == 0.f) continue;
-				const float4 od = rec[2 * ee];
-				o = xyz(od);
-				d = xyz(dd);
-				tmin = 0.f;
-				tmax = od.w;
-				any = true;
-				cur = ee;
-				++n_shadow;
-				got = true;
-				break;
-			}
-			if(!got && cl)
-			{
-				cl = false;
-				o = co;
-				d = cd;
-				tmin = ctmin;
-				tmax = ctmax;
-				any = false;
-				++n_closest;
-				got = true;
-			}
-			if(!got) break;
-			V3 dq = d;
-			if(fabsf(dq.x) < 1e-20f) dq.x = copysignf(1e-20f, dq.x);
-			if(fabsf(dq.y) < 1e-20f) dq.y = copysignf(1e-20f, dq.y);
-			if(fabsf(dq.z) < 1e-20f) dq.z = copysignf(1e-20f, dq.z);
-			id = v3(rcpExact(dq.x), rcpExact(dq.y), rcpExact(dq.z));
-			oid = v3(o.x * id.x, o.y * id.y, o.z * id.z);
-			sel = slabSel(id);
-			box_t0 = any ? -1e-3f : (tmin - 1e-3f * (1.f + fabsf(tmin)));
-			t_best = tmax;
-			prim_best = -1;
-			sp = 0;
-			node = 0;
-		}
-		if(STATS) TRACE_STAT(++visits);
-		const float4 *np = C.nodes + 8 * node;
-		const float4 nx = np[sel.nx], fx = np[sel.nx ^ 1], ny = np[sel.ny], fy = np[sel.ny ^ 1], nz = np[sel.nz], fz = np[sel.nz ^ 1], cf = np[6], kf = np[7];
-		const float slack_t = (t_best < 3.0e38f) ? t_best * 1.0000005f + 1e-6f : 3.4e38f;
-		float key[4];
-		int child[4], e4[4], s4[4];
-		int acc = 0;
-#pragma unroll
-		for(int k = 0; k < 4; ++k)
-		{
-			const float lo = fmaxf(fmaxf(__builtin_fmaf(lane4(nx, k), id.x, -oid.x), __builtin_fmaf(lane4(ny, k), id.y, -oid.y)),
-			                       fmaxf(__builtin_fmaf(lane4(nz, k), id.z, -oid.z), box_t0));
-			const float hi = fminf(fminf(__builtin_fmaf(lane4(fx, k), id.x, -oid.x), __builtin_fmaf(lane4(fy, k), id.y, -oid.y)),
-			                       fminf(__builtin_fmaf(lane4(fz, k), id.z, -oid.z), slack_t));
-			const uint32_t h = lo <= hi ? 1u : 0u;
-			child[k] = __float_as_int(lane4(cf, k));
-			const int count = __float_as_int(lane4(kf, k));
-			const uint32_t inner = child[k] >= 0 ? 1u : 0u;
-			key[k] = (h & inner) ? lo : inf;
-			s4[k] = ~child[k] - acc;
-			acc += (h & (inner ^ 1u)) ? count : 0;
-			e4[k] = acc;
-		}
-		bool done = false;
-		for(int i = 0; i < e4[3]; ++i)
-		{
-			const int q = i + (i < e4[0] ? s4[0] : i < e4[1] ? s4[1] : i < e4[2] ? s4[2] : s4[3]);
-			if(STATS) TRACE_STAT(++tests);
-			const float4 *tp = C.tris + 3 * q;
-			const float4 ta = tp[0], tb = tp[1], tc = tp[2];
-			const float t = triTest(ta, tb, tc, o, d, t_best);
-			if(t == -1.f) continue;
-			const int prim = __float_as_int(tb.w);
-			if(any)
-			{
-				if(t < tmax && t >= 0.f) { t_best = t; prim_best = prim; done = true; break; }
-			}
-			else if(t >= tmin && (t < t_best || (t == t_best && prim_best >= 0 && prim < prim_best)))
-			{
-				t_best = t;
-				prim_best = prim;
-			}
-		}
-		if(!done)
-		{
-			cswap(key[0], child[0], key[1], child[1]);
-			cswap(key[2], child[2], key[3], child[3]);
-			cswap(key[0], child[0], key[2], child[2]);
-			cswap(key[1], child[1], key[3], child[3]);
-			cswap(key[1], child[1], key[2], child[2]);
-			if(key[3] < inf) { C.stack[sp * STRIDE + lane] = child[3]; ++sp; }
-			if(key[2] < inf) { C.stack[sp * STRIDE + lane] = child[2]; ++sp; }
-			if(key[1] < inf) { C.stack[sp * STRIDE + lane] = child[1]; ++sp; }
-			int next = key[0] < inf ? child[0] : -1;
-			if(next < 0 && sp > 0)
-			{
-				--sp;
-				next = C.stack[sp * STRIDE + lane];
-			}
-			node = next;
-			done = next < 0;
-		}
-		if(done)
-		{
-			if(any) occ[cur] = prim_best >= 0 ? 1 : 0;
-			else
-			{
-				hit_t = t_best;
-				hit_prim = prim_best;
-			}
-			node = -1;
-		}
-	}
-}
 
 struct NeeArgs
 {
@@ -7192,7 +5962,7 @@ __global__ void __launch_bounds__(kTraceBlock) k_fg_first(FgPathArgs PA)
 			float t;
 			int prim;
 			++n_paths;
-			if(traverse<false, WIDE, SPILL, false, false, LDS_SCENE>(C, from, dir, S.ray_min_dist, __builtin_huge_valf(), t, prim, visits, tests))
+			if(traverse<false, WIDE, SPILL, false, false>(C, from, dir, S.ray_min_dist, __builtin_huge_valf(), t, prim, visits, tests))
 			{
 				const Surf hit = fgSurf<EXT>(S, from, dir, t, prim);
 				const uint32_t mat_bsd_fs = hit.flags;

@@ -853,8 +853,6 @@ bool GpuRenderer::upload(HostScene &hs)
 	if(const char *e = getenv("YAFARAY_AMD_LDS_STACK"); e && *e) d.lds_stack = std::min(d.stack_depth, std::max(4, atoi(e)));
 	const size_t scene_bytes = (size_t)(d.node_f4 * d.n_nodes + 3 * d.n_tris) * 16;
 	d.scene_in_lds = scene_bytes + (size_t)d.lds_stack * yafamd_trace_block() * 4 <= 48 * 1024;
-	// (k_trace's packed child keys carry a node index in 9 bits: 48 KB holds at most 384 BVH4 nodes)
-	if(d.node_f4 == 8 && d.n_nodes >= 512) d.scene_in_lds = false;
 	if(const char *e = getenv("YAFARAY_AMD_SCENE_LDS"); e && *e == '0') d.scene_in_lds = false;   // tests: global-memory traversal on small scenes
 	// a BVH4 in global memory: k_trace's refill loop reads the top treelet (the first levels, which
 	// every ray visits) from LDS — 21 nodes = the root and two full levels below it, 2.7 KB per
@@ -868,7 +866,7 @@ bool GpuRenderer::upload(HostScene &hs)
 		// the treelet and the stack share the workgroup's LDS: clamp the treelet so that k_trace still
 		// launches — 64 KB per workgroup, the launch limit
 		const size_t stack_b = (size_t)d.lds_stack * yafamd_trace_block() * 4, lds_max = 64 * 1024;
-		const int fit = stack_b >= lds_max ? 0 : (int)((lds_max - stack_b) / 144);   // 144 B per staged node (kernels.hip kTopStride)
+		const int fit = stack_b >= lds_max ? 0 : (int)((lds_max - stack_b) / 144);   // 144 B per staged node (trace.h kTopStride)
 		if(d.lds_top > fit)
 		{
 			log_.warning("GPU: YAFARAY_AMD_LDS_TOP=" + std::to_string(d.lds_top) + " does not fit the trace workgroup's LDS; using " +
@@ -876,7 +874,7 @@ bool GpuRenderer::upload(HostScene &hs)
 			d.lds_top = fit;
 		}
 	}
-	// the BVH8's top treelet: the root and its eight children (80 B per node, kernels.hip kTop8Stride)
+	// the BVH8's top treelet: the root and its eight children (80 B per node, trace.h kTop8Stride)
 	d.lds_top8 = 0;
 	if(d.nodes8.p && !d.scene_in_lds)
 	{
@@ -893,7 +891,7 @@ bool GpuRenderer::upload(HostScene &hs)
 		                   (d.scene_in_lds ? scene_bytes : w8 ? (size_t)d.lds_top8 * 80 : (size_t)d.lds_top * 144);
 		const int per_cu = std::max(1, yafamd_trace_blocks_per_cu(d.scene_in_lds ? 1 : 0, w8 ? 8 : (d.node_f4 == 8 ? 1 : 0), dyn, 0));
 		d.trace_grid = d.n_cu * per_cu;
-		// Deferred leaf tests in k_trace's plain BVH4 loop (kernels.hip traverse4Defer): LDS-resident
+		// Deferred leaf tests in k_trace's plain BVH4 loop (trace.h traverse4Defer): LDS-resident
 		// scenes without a spill column whose leaves fit the 16-bit list entries.  The per-lane lists (2 B per
 		// entry and lane) follow the scene in LDS and never cost a resident workgroup: the capacity
 		// (YAFARAY_AMD_TRACE_DEFER_CAP, default 8 leaves) shrinks until the kernel keeps the grid above, and a scene

@@ -2,7 +2,7 @@
 
 yafaray_amd_traceQueued (Interface.trace_queued) builds the queues, counters and launch parameters a render
 hands yafamd_launch_trace, so the kernel that runs is the one a render of the scene launches under the same
-environment: the LDS-resident BVH4 (packed child keys) with and without the spill column and statistics, the
+environment: the LDS-resident BVH4 (traverse4) with and without the spill column and statistics, the
 LDS-resident BVH2, the plain loop over a BVH2 in global memory, traceRefill4 (BVH4 in global memory, LDS top
 treelet) and traceRefill8 (the quantised BVH8), and the closest-only / shadow-only launches of the overlapped
 schedule.  The rays are the classes of tests/raylib.py; the reference is the oracle's loop over every triangle

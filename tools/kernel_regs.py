@@ -1,6 +1,8 @@
 """VGPR / SGPR / scratch / LDS of the kernels in a built library (or object): the gfx950 code object is
 taken out of the .hip_fatbin section and its AMDGPU metadata printed.
-   python tools/kernel_regs.py libyafaray_amd/libyafaray4.so [name-substring ...]"""
+   python tools/kernel_regs.py libyafaray_amd/libyafaray4.so [name-substring ...]
+   python tools/kernel_regs.py --text-hash OBJECT_OR_LIBRARY ...   (size and sha256 of the gfx950 .text)"""
+import hashlib
 import os
 import re
 import subprocess
@@ -20,7 +22,21 @@ def code_object(path, tmp):
     return co
 
 
+def text_hash(path):
+    """size and sha256 of the gfx950 .text: two builds with the same line run the same device code"""
+    with tempfile.TemporaryDirectory() as tmp:
+        text = os.path.join(tmp, "text")
+        subprocess.run([f"{B}/llvm-objcopy", "-O", "binary", "--only-section=.text", code_object(path, tmp), text], check=True)
+        with open(text, "rb") as f:
+            data = f.read()
+    print(f"{path}: gfx950 .text {len(data)} bytes sha256 {hashlib.sha256(data).hexdigest()}")
+
+
 def main():
+    if sys.argv[1] == "--text-hash":
+        for path in sys.argv[2:]:
+            text_hash(path)
+        return
     path, pats = sys.argv[1], sys.argv[2:]
     with tempfile.TemporaryDirectory() as tmp:
         notes = subprocess.run([f"{B}/llvm-readelf", "--notes", code_object(path, tmp)], capture_output=True, text=True).stdout
