@@ -591,6 +591,27 @@ struct DevStats
 	unsigned long long pre_visits;       // k_pregather: diffuse-map kd nodes fetched
 	unsigned long long pre_photons;      // k_pregather: photons summed into the radiance estimates
 };
+// every counter of `b` added to `a` (the host sums the per-workgroup records); a new field is added here too
+inline DevStats &operator+=(DevStats &a, const DevStats &b)
+{
+	a.closest_rays += b.closest_rays;
+	a.shadow_rays += b.shadow_rays;
+	a.node_visits += b.node_visits;
+	a.tri_tests += b.tri_tests;
+	a.shade_entries += b.shade_entries;
+	a.nee_requests += b.nee_requests;
+	a.gather_queries += b.gather_queries;
+	a.gather_visits += b.gather_visits;
+	a.gather_photons += b.gather_photons;
+	a.gather_accepts += b.gather_accepts;
+	a.gather_overflows += b.gather_overflows;
+	a.fg_paths += b.fg_paths;
+	a.fg_lookups += b.fg_lookups;
+	a.fg_nearest_visits += b.fg_nearest_visits;
+	a.pre_visits += b.pre_visits;
+	a.pre_photons += b.pre_photons;
+	return a;
+}
 
 // the two-pass diffuse gather's accepted-photon log for one batch of the gather queue (kernels.hip
 // GatherLog): cap entries of 8 bytes per request, seg_cap queue positions per segment from j0

@@ -6188,6 +6188,18 @@ __global__ void __launch_bounds__(256) k_fg_sum(FgPathArgs PA)
 // ---------------------------------------------------------------------------------------------
 using namespace yafamd;
 
+// The lean scene: the plain path tracer, one path per sample, with none of the stages that need the full path
+// record (AO, photon maps and their display, a recursion tree, surface attributes).  The one definition behind
+// every wrapper's choice of k_shade below, so the render (which asks yafamd_shade_fused_for / _stages_for) and
+// the launch cannot disagree on which kernel runs.
+static bool leanScene(const DevScene &S)
+{
+	return S.integrator == INT_PATH && S.path_samples <= 1 && !S.do_ao && !S.caus_map && !S.gather_on && !S.show_map && S.n_photons == 0 && !S.tree &&
+	       !S.has_attr && !S.no_lean;
+}
+// yafamd_launch_shade launches one of the lean k_shade kernels for the scene (neither EXT nor the all-fused tuning build)
+static bool leanShade(const DevScene &S) { return !S.ext && !kShadeFused && leanScene(S); }
+
 extern "C" {
 
 int yafamd_trace_block() { return kTraceBlock; }
@@ -6205,17 +6217,12 @@ int yafamd_shade_fused_for(const DevScene *S)
 {
 	if(S->ext) return 0;
 	if(kShadeFused) return 1;
-	return (YAF_FUSE_LEAN && S->integrator == INT_PATH && S->path_samples <= 1 && !S->do_ao && !S->caus_map && !S->gather_on && !S->show_map &&
-	        S->n_photons == 0 && !S->tree && !S->has_attr && !S->no_lean && !S->tr_shad && !S->has_mesh_light && !S->has_ext_light) ? 1 : 0;
+	return (YAF_FUSE_LEAN && leanScene(*S) && !S->tr_shad && !S->has_mesh_light && !S->has_ext_light) ? 1 : 0;
 }
 
 // The scene's k_shade is the lean non-fused kernel (yafamd_launch_shade's choice below) over compact records
 // without a recursion tree: its launches may be stage-specialised (SG_*) while S->lpc_mode == 0
-int yafamd_shade_stages_for(const DevScene *S)
-{
-	return (!S->ext && !kShadeFused && S->integrator == INT_PATH && S->path_samples <= 1 && !S->do_ao && !S->caus_map && !S->gather_on && !S->show_map &&
-	        S->n_photons == 0 && !S->tree && !S->has_attr && !S->no_lean && !yafamd_shade_fused_for(S)) ? 1 : 0;
-}
+int yafamd_shade_stages_for(const DevScene *S) { return (leanShade(*S) && !yafamd_shade_fused_for(S)) ? 1 : 0; }
 
 // The stage guard's words (g_shade_stage_err), read and cleared: the entries that iteration k's stage-specialised
 // k_shade found in another stage (the last word: every later iteration)
@@ -6448,9 +6455,7 @@ hipError_t yafamd_launch_shade(const DevScene *S, const DevPaths *Pc, const DevP
 	{
 		// the deferred light pick's path pass (yafamd_dfr_eligible scenes only)
 		if(S->ext || S->tree || S->gather_on) return hipErrorInvalidValue;
-		const bool lean = S->integrator == INT_PATH && S->path_samples <= 1 && !S->do_ao && !S->caus_map && !S->show_map && S->n_photons == 0 &&
-		                  !S->has_attr && !S->no_lean;
-		if(lean) { if(S->small_tables) hipLaunchKernelGGL((k_shade<true, false, false, true, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
+		if(leanScene(*S)) { if(S->small_tables) hipLaunchKernelGGL((k_shade<true, false, false, true, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
 		           else hipLaunchKernelGGL((k_shade<false, false, false, true, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A); }
 		else if(S->small_tables) hipLaunchKernelGGL((k_shade<true, false, false, false, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
 		else hipLaunchKernelGGL((k_shade<false, false, false, false, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
@@ -6461,8 +6466,7 @@ hipError_t yafamd_launch_shade(const DevScene *S, const DevPaths *Pc, const DevP
 		if(S->small_tables) hipLaunchKernelGGL((k_shade<true, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
 		else hipLaunchKernelGGL((k_shade<false, true>), dim3(S->n_seg), dim3(kShadeBlock), lds, st, A);
 	}
-	else if(!kShadeFused && S->integrator == INT_PATH && S->path_samples <= 1 && !S->do_ao && !S->caus_map && !S->gather_on && !S->show_map &&
-	        S->n_photons == 0 && !S->tree && !S->has_attr && !S->no_lean)
+	else if(leanShade(*S))
 	{
 		if(yafamd_shade_fused_for(S))
 		{

@@ -1885,19 +1885,153 @@ bool GpuRenderer::buildPhotonMap(RenderParams &rp)
 	return true;
 }
 
+// Which launch sequence a render runs (Run::decideSchedule; the gather's and the ray binning's switches come from
+// the setup steps that allocate for them)
+struct Schedule
+{
+	bool overlap = false;                          // the next iteration's closest rays on the side stream, beside k_nee
+	int ov_nee_grid = 0, ov_trace_grid = 0;        // ... their grids
+	bool ov_shadow = false;                        // the shadow part beside the side stream's closest part
+	int ov_shadow_grid = 0;
+	bool defer_it0 = false;                        // k_trace's deferred leaf lists in iteration 0 too
+	bool ray_bin = false;                          // the bounce rays sorted before k_trace
+	int nee_trace_stack = 0;                       // > 0: k_nee traces its shadow rays in place, with this LDS stack
+	bool lpc_on = false;                           // the one-thread light pick (count run or deferred pick per pass)
+	bool shade_stages = false;                     // stage-specialised k_camera / k_shade launches
+	int path_grid = 0;                             // > 0: the megakernel on this grid instead of the wavefront
+	bool walk_gather = false, fg_paths = false;    // the two-pass diffuse gather; final gathering with one lane per path
+	int iters = 0;                                 // wavefront iterations per chunk
+};
+
+// the adaptive passes' bookkeeping (TiledIntegrator::render, integrator_tiled.cc:172-231)
+struct AaState
+{
+	float threshold = 0.f, sample_multiplier = 1.f, light_multiplier = 1.f, indirect_multiplier = 1.f;
+	bool threshold_changed = true;
+	int acum = 0;              // samples per pixel of the passes so far
+	int resampled = 0;         // pixels nextPass flagged in the whole film
+	int resampled_local = 0;   // of them in this member's rows (+ halo rows): the pixels it renders
+};
+
+// A launch beside side-stream work that fails leaves none of that work behind: the stream is synchronised on
+// every exit but the successful one
+struct SideSync
+{
+	hipStream_t side;
+	bool ok = false;
+	~SideSync() { if(!ok) (void)hipStreamSynchronize(side); }
+};
+
+// One render() call: the values its stages share, and the stages in call order.  S, rp.film and d.Q[*] are copied
+// by value at every launch, so an assignment to them takes effect for the launches after it only.
+struct GpuRenderer::Run
+{
+	Run(GpuRenderer &r_, RenderParams &rp_, volatile bool *canceled_)
+	    : r(r_), log_(r_.log_), d_(r_.d_), stats_(r_.stats_), ktimes_(r_.ktimes_), owned_rows_(r_.owned_rows_), sampling_offset_(r_.sampling_offset_),
+	      passes_done_(r_.passes_done_), lpc_carry_(r_.lpc_carry_), d(*r_.d_), rp(rp_), S(rp_.scene), canceled(canceled_),
+	      group_render(!rp_.band_bounds.empty() && r_.grouped()), n_lay((int)rp_.layers.kinds.size()),
+	      light_mult(rp_.aa.passes > 1 && rp_.aa.light_sample_multiplier_factor != 1.f), passes(std::max(1, rp_.aa.passes))
+	{
+	}
+
+	// the renderer, and its members that a render sets, under their own names (HIPCHECK and PROF use log_ and d_)
+	GpuRenderer &r;
+	Logger &log_;
+	Impl *d_;
+	yafaray_amd_stats_t &stats_;
+	KernelTimes &ktimes_;
+	std::vector<std::pair<int, int>> &owned_rows_;
+	uint32_t &sampling_offset_;
+	int &passes_done_;
+	uint32_t &lpc_carry_;
+	Impl &d;
+	RenderParams &rp;
+	DevScene &S;
+	volatile bool *canceled;
+
+	const bool group_render;   // the members meet between adaptive passes (status + accumulator exchange)
+	const int n_lay;           // render layers
+	const bool light_mult;     // AA_light_sample_multiplier_factor changes the NEE layout per pass
+	const int passes;
+	unsigned long long xl0 = 0;   // yafamd_xl_launches() before the render
+	int W = 0, H = 0, spp = 0, ts = 0;
+	int n_jobs = 0, jy0 = 0, jy1 = 0;   // d.jobs; the rows they cover
+	uint64_t total = 0;                 // camera samples of pass 0 (owned + halo rows)
+	DevLayers LY{};
+	uint64_t layer_rays = 0;   // closest rays of the first-hit pass and of the depth pre-pass
+	size_t M = 0;              // samples in flight: the chunk
+	size_t R = 0;              // queue segments
+	GatherLogDesc glog{nullptr, nullptr, 0u, 0u, 0u, 0u, 0u};
+	FgBatch fgb{};
+	DevCounters cnt[2];
+	DevStats *dstats = nullptr;
+	DevStats *run_stats = nullptr;   // the light-pick count runs count into their own statistics
+	Schedule sch;
+	bool shade_staged = false;           // some k_shade launch was stage-specialised: its guard words are read after the render
+	bool tree_overflow_logged = false;
+	uint64_t done = 0;                   // samples of the last runSamples' chunks that ran (< n_total only when canceled)
+	uint64_t samples_total = 0;
+
+	// setup, in call order
+	bool prepareScene();
+	bool planJobs();
+	bool allocFrame();
+	bool ensureLayerBufs(std::initializer_list<std::pair<Buf *, size_t>> want);
+	bool setupLayers();
+	int layoutLights(float mult, std::vector<DevLight> &ls);
+	bool allocChunk();
+	bool setupGather();
+	bool setupRayBin();
+	bool setupCounters();
+	bool decideSchedule();
+	bool startClock();
+	// the wavefront
+	bool launchShadowBesideClosest(const DevQueues &qc, int cur);
+	bool launchNeeBesideNextClosest(int cur);
+	bool fgPrepare();
+	bool launchGathers(int cur, uint64_t base);
+	bool iterate(uint64_t base);
+	bool runSamples(uint64_t n_total);
+	bool runTreeLevels(uint64_t base, int n);
+	// one pass with the one-thread light pick (0 is "failed" in both, which HIPCHECK's `return false` yields)
+	enum : int { LPC_FAILED = 0, LPC_HASH, LPC_COUNTERS };
+	enum : int { DFR_FAILED = 0, DFR_KEPT, DFR_COUNT_RUN };
+	bool runPass(uint64_t n_total, int pass_spp);
+	int lpcBudget(size_t n_ctr);
+	int runDeferredPick(uint64_t n_total, int pass_spp, size_t n_ctr);
+	bool runCountThenRender(uint64_t n_total, int pass_spp, size_t n_ctr);
+	// passes and film
+	bool runLayerHits(uint64_t n_done);
+	bool layerFilm(const DevFilm &F, const uint8_t *flags, void *out, int y0, int y1, int accumulate);
+	bool filmRows(const DevFilm &F, const uint8_t *flags, int accumulate);
+	bool setupFilm();
+	bool emitTiles(int pass, const uint8_t *flags, int accumulate);
+	bool firstPass();
+	bool dumpAaFlags(int pass);
+	bool adaptivePasses();
+	bool checkStageGuard();
+	bool finish();
+};
+
 bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 {
 	if(!ready()) return false;
 	DeviceGuard guard(device_);
-	Impl &d = *d_;
-	// a group render: the members meet between adaptive passes (status + accumulator exchange)
-	const bool group_render = !rp.band_bounds.empty() && grouped();
+	Run run(*this, rp, canceled);
+	// the stages in call order ("anatomy of a render"); each logs its own failure
+	return run.prepareScene() && run.planJobs() && run.allocFrame() && run.setupLayers() && run.allocChunk() && run.setupGather() &&
+	       run.setupRayBin() && run.setupCounters() && run.decideSchedule() && run.startClock() && run.setupFilm() && run.firstPass() &&
+	       run.adaptivePasses() && run.finish();
+}
+
+// the group's bounds, the scene's device pointers, the render's statistics and the photon maps
+bool GpuRenderer::Run::prepareScene()
+{
 	if(group_render && ((int)rp.band_bounds.size() != rp.shard_world + 1 || rp.shard_mode != 2))
 	{
 		log_.error("GPU group: band bounds do not match the group");
 		return false;
 	}
-	DevScene &S = rp.scene;
 	fillScenePointers(d, S);
 	stats_.photons = 0;
 	stats_.photon_paths_traced = stats_.photon_slots = 0;
@@ -1910,7 +2044,7 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 	d.ev_n = 2;
 	d.prof_recs.clear();
 	ktimes_ = KernelTimes{};
-	const unsigned long long xl0 = yafamd_xl_launches();
+	xl0 = yafamd_xl_launches();
 	S.caus_map = 0;
 	S.gather_on = 0;
 	S.n_photons = 0;
@@ -1931,7 +2065,7 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		// PhotonIntegrator::preprocess (integrator_photon_mapping.cc:242-638) / createCausticMap
 		// (integrator_montecarlo.cc:565-625): the photon maps are rebuilt for every render, as the
 		// reference's "generate" mode does
-		if(!buildPhotonMap(rp)) return false;
+		if(!r.buildPhotonMap(rp)) return false;
 		if(S.fg_on && S.tr_shad &&
 		   !ensure(log_, d.fg_ts, (size_t)d.trace_grid * yafamd_trace_block() * (size_t)std::max(1, S.s_depth) * sizeof(float2)))
 			return false;
@@ -1941,8 +2075,13 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 			return false;
 		}
 	}
-	const int W = S.width, H = S.height, spp = S.spp, ts = S.tile;
-	// ---- jobs: owned rows (+ halo rows for the film gather when sharded) ----
+	W = S.width, H = S.height, spp = S.spp, ts = S.tile;
+	return true;
+}
+
+// ---- jobs: owned rows (+ halo rows for the film gather when sharded) ----
+bool GpuRenderer::Run::planJobs()
+{
 	// shard_mode 1: one contiguous band of H / world pixel rows per rank (per-row cost is nearly
 	// uniform, so equal bands balance the GPUs and only one halo row is rendered twice);
 	// shard_mode 0: whole tile rows r % world == rank.  Either way every owned pixel gets exactly the
@@ -1950,7 +2089,7 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 	const int tile_rows = (H + ts - 1) / ts;
 	std::vector<DevJob> jobs;
 	owned_rows_.clear();
-	uint64_t total = 0;
+	total = 0;
 	if(rp.shard_world <= 1) owned_rows_.push_back({0, H});
 	else if(rp.shard_mode == 2)
 	{
@@ -1989,8 +2128,20 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		}
 	}
 	if(!allocCopy(log_, d.jobs, jobs.data(), jobs.size())) return false;
-	const int n_jobs = (int)jobs.size();
-	// ---- frame buffers ----
+	n_jobs = (int)jobs.size();
+	// the rows the jobs cover (lpcBases)
+	jy0 = H, jy1 = 0;
+	for(const DevJob &j : jobs)
+	{
+		jy0 = std::min(jy0, j.y0);
+		jy1 = std::max(jy1, j.y1);
+	}
+	return true;
+}
+
+// ---- frame buffers ----
+bool GpuRenderer::Run::allocFrame()
+{
 	if(!ensure(log_, d.samples, (size_t)W * H * spp * sizeof(float4))) return false;
 	if(!ensure(log_, d.film, (size_t)W * H * sizeof(float4))) return false;
 	if(!ensure(log_, d.accum, (size_t)W * H * sizeof(float4))) return false;
@@ -2007,34 +2158,38 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		HIPCHECK(hipMemcpyAsync(d.weights.p, rp.load_weights, (size_t)W * H * sizeof(float), hipMemcpyHostToDevice, d.stream));
 		HIPCHECK(hipStreamSynchronize(d.stream));
 	}
-	// ---- render layers (layers_kernels.h): only a render that defines any allocates or launches anything ----
-	const int n_lay = (int)rp.layers.kinds.size();
-	DevLayers LY{};
+	return true;
+}
+
+// layer buffers that are not allocated yet (or too small) have to fit the free device memory
+bool GpuRenderer::Run::ensureLayerBufs(std::initializer_list<std::pair<Buf *, size_t>> want)
+{
+	size_t fresh = 0;
+	for(const auto &w : want)
+		if(w.second && !(w.first->p && w.first->bytes >= w.second)) fresh += w.second;
+	size_t free_b = 0, total_b = 0;
+	if(fresh && hipMemGetInfo(&free_b, &total_b) == hipSuccess && fresh > free_b)
+	{
+		log_.error("Layers: the layer buffers (" + std::to_string(fresh >> 20) + " MB) exceed the free device memory (" + std::to_string(free_b >> 20) +
+		           " MB); define fewer layers or render fewer samples per pass");
+		return false;
+	}
+	for(const auto &w : want)
+		if(w.second && !ensure(log_, *w.first, w.second)) return false;
+	return true;
+}
+
+// ---- render layers (layers_kernels.h): only a render that defines any allocates or launches anything ----
+bool GpuRenderer::Run::setupLayers()
+{
 	d.n_layers = n_lay;
-	uint64_t layer_rays = 0;   // closest rays of the first-hit pass and of the depth pre-pass
 	const size_t lay_plane = (size_t)W * H * sizeof(float4);
-	const bool lay_tiles = n_lay > 0 && (bool)rp.on_tiles && rp.shard_world == 1 && groupWorld() <= 1;
+	const bool lay_tiles = n_lay > 0 && (bool)rp.on_tiles && rp.shard_world == 1 && r.groupWorld() <= 1;
 	if(n_lay > LK_COUNT)
 	{
 		log_.error("Layers: more layers than the GPU core produces");
 		return false;
 	}
-	// layer buffers that are not allocated yet (or too small) have to fit the free device memory
-	auto ensureLayerBufs = [&](std::initializer_list<std::pair<Buf *, size_t>> want) -> bool {
-		size_t fresh = 0;
-		for(const auto &w : want)
-			if(w.second && !(w.first->p && w.first->bytes >= w.second)) fresh += w.second;
-		size_t free_b = 0, total_b = 0;
-		if(fresh && hipMemGetInfo(&free_b, &total_b) == hipSuccess && fresh > free_b)
-		{
-			log_.error("Layers: the layer buffers (" + std::to_string(fresh >> 20) + " MB) exceed the free device memory (" + std::to_string(free_b >> 20) +
-			           " MB); define fewer layers or render fewer samples per pass");
-			return false;
-		}
-		for(const auto &w : want)
-			if(w.second && !ensure(log_, *w.first, w.second)) return false;
-		return true;
-	};
 	// a render without layers keeps none of an earlier render's layer buffers
 	if(n_lay == 0)
 		for(Buf *b : {&d.lay_rec, &d.lay_albedo, &d.lay_accum, &d.lay_film, &d.lay_pfilm, &d.lay_mat, &d.lay_obj, &d.lay_depth}) b->release();
@@ -2110,8 +2265,37 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 			LY.depth = (const float *)d.lay_depth.p;
 		}
 	}
-	// ---- chunk buffers ----
-	size_t M = (size_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)rp.chunk_slots, std::max<uint64_t>(total, 1)));
+	return true;
+}
+
+// AA_light_sample_multiplier_factor: pass p draws ceilf(samples * factor^p) samples per area light
+// (integrator_montecarlo.cc:396), so the NEE layout changes per pass: the lights with `mult` applied and
+// S.nee_all_count set for them; returns the NEE entries per sample that layout needs
+int GpuRenderer::Run::layoutLights(float mult, std::vector<DevLight> &ls)
+{
+	ls = d.host_lights;
+	uint32_t base = 0, max_one = 1;
+	for(DevLight &L : ls)
+	{
+		if(L.photon_only) continue;   // no NEE entries (after the visible lights)
+		if(L.type == LIGHT_AREA || L.type == LIGHT_MESH || L.type == LIGHT_SUN || L.type == LIGHT_SPHERE)
+		{
+			L.samples = (int)ceilf((float)L.samples * mult);
+			L.inv_samples = 1.f / (float)L.samples;
+			L.nee_count = 2u * (uint32_t)std::max(0, L.samples);
+		}
+		L.nee_base = base;
+		base += L.nee_count;
+		max_one = std::max(max_one, L.nee_count);
+	}
+	S.nee_all_count = (int)base;
+	return (int)std::max(base + (S.do_ao ? (uint32_t)S.ao_samples : 0u), max_one);
+}
+
+// ---- chunk buffers ----
+bool GpuRenderer::Run::allocChunk()
+{
+	M = (size_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)rp.chunk_slots, std::max<uint64_t>(total, 1)));
 	// a group member's band moves from frame to frame (rebalanceBands): the chunk buffers hold twice an equal
 	// share, so a band that grows does not re-allocate them (GBs, hipFree + hipMalloc) between timed frames
 	if(rp.shard_world > 1)
@@ -2142,28 +2326,7 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		S.spawn_count = (uint32_t *)d.spawn_count.p;
 	}
 	S.cur_level = 0;
-	// AA_light_sample_multiplier_factor: pass p draws ceilf(samples * factor^p) samples per area light
-	// (integrator_montecarlo.cc:396), so the NEE layout changes per pass; size it for the largest
-	const bool light_mult = rp.aa.passes > 1 && rp.aa.light_sample_multiplier_factor != 1.f;
-	auto lightLayout = [&](float mult, std::vector<DevLight> &ls) -> int {
-		ls = d.host_lights;
-		uint32_t base = 0, max_one = 1;
-		for(DevLight &L : ls)
-		{
-			if(L.photon_only) continue;   // no NEE entries (after the visible lights)
-			if(L.type == LIGHT_AREA || L.type == LIGHT_MESH || L.type == LIGHT_SUN || L.type == LIGHT_SPHERE)
-			{
-				L.samples = (int)ceilf((float)L.samples * mult);
-				L.inv_samples = 1.f / (float)L.samples;
-				L.nee_count = 2u * (uint32_t)std::max(0, L.samples);
-			}
-			L.nee_base = base;
-			base += L.nee_count;
-			max_one = std::max(max_one, L.nee_count);
-		}
-		S.nee_all_count = (int)base;
-		return (int)std::max(base + (S.do_ao ? (uint32_t)S.ao_samples : 0u), max_one);
-	};
+	// the NEE layout changes per pass with AA_light_sample_multiplier_factor (layoutLights); size it for the largest
 	if(light_mult)
 	{
 		float mult = 1.f;
@@ -2171,16 +2334,16 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		for(int p = 1; p < rp.aa.passes; ++p)
 		{
 			mult *= rp.aa.light_sample_multiplier_factor;
-			S.nee_k = std::max(S.nee_k, lightLayout(mult, tmp));
+			S.nee_k = std::max(S.nee_k, layoutLights(mult, tmp));
 		}
-		lightLayout(1.f, tmp);
+		layoutLights(1.f, tmp);
 	}
 	const int K = std::max(1, S.nee_k);
 	const bool need_v0 = S.path_samples > 1 || S.integrator == INT_PHOTON || S.caus_map;
 	const bool need_g = S.gather_on != 0;
 	// segment capacity: the camera deals groups of 256 samples round-robin over the segments
-	const size_t R = (size_t)d.shade_grid;
-	auto shardCap = [R](size_t m) { return (((m + 255) / 256 + R - 1) / R) * 256; };
+	R = (size_t)d.shade_grid;
+	auto shardCap = [R = R](size_t m) { return (((m + 255) / 256 + R - 1) / R) * 256; };
 	const bool need_attr = S.has_attr != 0;
 	const int need_ts = S.tr_shad ? std::max(1, S.s_depth) : 0;
 	const bool need_tree = S.tree != 0;   // the full record (slot + col.w stage) only with a specular recursion tree
@@ -2275,47 +2438,52 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 	S.n_seg = (uint32_t)R;
 	S.cap_a = (uint32_t)shardCap(d.slots_cap);
 	S.cap_s = S.cap_a * (uint32_t)K;
-	// The two-pass diffuse gather (k_gather_walk + k_gather<REPLAY>, kernels.hip): its log holds `cap`
-	// logged photons per request for a batch of
-	// seg_cap queue positions per segment (within 16 GB); YAFARAY_AMD_GATHER=single keeps one pass.
-	GatherLogDesc glog{nullptr, nullptr, 0u, 0u, 0u, 0u, 0u};
-	bool walk_gather = false;
+	return true;
+}
+
+// The two-pass diffuse gather (k_gather_walk + k_gather<REPLAY>, kernels.hip): its log holds `cap`
+// logged photons per request for a batch of
+// seg_cap queue positions per segment (within 16 GB); YAFARAY_AMD_GATHER=single keeps one pass.
+bool GpuRenderer::Run::setupGather()
+{
+	const char *ge = std::getenv("YAFARAY_AMD_GATHER");
+	const bool single = ge && std::string(ge) == "single";
+	if(S.gather_on && S.n_photons > 0 && S.pm_search <= yafamd_gather_walk_k() && !single)
 	{
-		const char *ge = std::getenv("YAFARAY_AMD_GATHER");
-		const bool single = ge && std::string(ge) == "single";
-		if(S.gather_on && S.n_photons > 0 && S.pm_search <= yafamd_gather_walk_k() && !single)
+		const char *ce = std::getenv("YAFARAY_AMD_GATHER_LOG");
+		const uint32_t cap = ((uint32_t)std::max(S.pm_search, ce ? atoi(ce) : 512) + 1u) & ~1u;   // even: pairs
+		size_t seg_cap = S.cap_a;
+		while((size_t)R * seg_cap * cap * 8 > (16ull << 30) && seg_cap > 64) seg_cap = ((seg_cap / 2 + 63) / 64) * 64;
+		if(!ensure(log_, d.g_log, (size_t)R * seg_cap * cap * 8) || !ensure(log_, d.g_log_n, (size_t)R * seg_cap * 4)) return false;
+		const char *he = std::getenv("YAFARAY_AMD_GATHER_HEAP");
+		const uint32_t split = (he && std::string(he) == "packed") ? 0u : 1u;
+		const char *we = std::getenv("YAFARAY_AMD_GATHER_WALK");
+		// the walk with the k smallest distances in registers (k <= 64): the bounded walk
+		// (YAFARAY_AMD_GATHER_WALK=bound, experiments builds; there also any k > 64) measured slower on C5
+		// (walk 13.9 -> 16.3 ms, replay 7.4 -> 12.1 ms per frame: its superset log); without it a larger
+		// k takes the one-pass gather (yafamd_gather_walk_k)
+		const uint32_t exact = (yafamd_experiments() && we && std::string(we) == "bound") ? 0u : 1u;
+		glog = GatherLogDesc{d.g_log.p, (uint32_t *)d.g_log_n.p, cap, (uint32_t)seg_cap, 0u, split, exact, nullptr};
+		// the walk's far-child stack levels beyond the LDS ones (tuning builds: -DYAF_WALK_LDS_LEVELS)
+		const int lv = yafamd_walk_lds_levels(d.pm_stack), deep = std::max(1, d.pm_stack) - lv;
+		if(deep > 0)
 		{
-			const char *ce = std::getenv("YAFARAY_AMD_GATHER_LOG");
-			const uint32_t cap = ((uint32_t)std::max(S.pm_search, ce ? atoi(ce) : 512) + 1u) & ~1u;   // even: pairs
-			size_t seg_cap = S.cap_a;
-			while((size_t)R * seg_cap * cap * 8 > (16ull << 30) && seg_cap > 64) seg_cap = ((seg_cap / 2 + 63) / 64) * 64;
-			if(!ensure(log_, d.g_log, (size_t)R * seg_cap * cap * 8) || !ensure(log_, d.g_log_n, (size_t)R * seg_cap * 4)) return false;
-			const char *he = std::getenv("YAFARAY_AMD_GATHER_HEAP");
-			const uint32_t split = (he && std::string(he) == "packed") ? 0u : 1u;
-			const char *we = std::getenv("YAFARAY_AMD_GATHER_WALK");
-			// the walk with the k smallest distances in registers (k <= 64): the bounded walk
-			// (YAFARAY_AMD_GATHER_WALK=bound, experiments builds; there also any k > 64) measured slower on C5
-			// (walk 13.9 -> 16.3 ms, replay 7.4 -> 12.1 ms per frame: its superset log); without it a larger
-			// k takes the one-pass gather (yafamd_gather_walk_k)
-			const uint32_t exact = (yafamd_experiments() && we && std::string(we) == "bound") ? 0u : 1u;
-			glog = GatherLogDesc{d.g_log.p, (uint32_t *)d.g_log_n.p, cap, (uint32_t)seg_cap, 0u, split, exact, nullptr};
-			// the walk's far-child stack levels beyond the LDS ones (tuning builds: -DYAF_WALK_LDS_LEVELS)
-			const int lv = yafamd_walk_lds_levels(d.pm_stack), deep = std::max(1, d.pm_stack) - lv;
-			if(deep > 0)
-			{
-				if(!ensure(log_, d.walk_spill, (size_t)deep * yafamd_walk_threads(&S) * 4)) return false;
-				glog.spill = (uint32_t *)d.walk_spill.p;
-			}
-			walk_gather = true;
+			if(!ensure(log_, d.walk_spill, (size_t)deep * yafamd_walk_threads(&S) * 4)) return false;
+			glog.spill = (uint32_t *)d.walk_spill.p;
 		}
+		sch.walk_gather = true;
 	}
 	// final gathering with one lane per gather path (kernels.hip k_fg_first / k_fg_long / k_fg_sum): its batch
-	// buffers, sized for the pass's path count (AA_indirect_sample_multiplier_factor changes it per pass) with
-	// room for every path to bounce (no overflow); a batch is seg_cap request positions of every segment,
+	// buffers (fgPrepare), sized for the pass's path count (AA_indirect_sample_multiplier_factor changes it per pass)
+	// with room for every path to bounce (no overflow); a batch is seg_cap request positions of every segment,
 	// within 6 GB
-	const bool fg_paths = yafamd_fg_paths_eligible(&S) != 0;
-	// ray binning for the BVH8 refill loop (opt-in experiment, YAFARAY_AMD_RAY_BIN=1): sort keys and the permutation
-	bool ray_bin = false;
+	sch.fg_paths = yafamd_fg_paths_eligible(&S) != 0;
+	return true;
+}
+
+// ray binning for the BVH8 refill loop (opt-in experiment, YAFARAY_AMD_RAY_BIN=1): sort keys and the permutation
+bool GpuRenderer::Run::setupRayBin()
+{
 	if(const char *e = std::getenv("YAFARAY_AMD_RAY_BIN"); e && *e == '1' && S.nodes8 && !S.scene_in_lds && !S.tr_shad && R <= 1024)
 	{
 		const size_t n = (size_t)R * S.cap_a;
@@ -2324,32 +2492,20 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		if(!ensure(log_, d.bin_keys, n * 4) || !ensure(log_, d.bin_keys2, n * 4) || !ensure(log_, d.bin_iota, n * 4) || !ensure(log_, d.bin_perm, n * 4) ||
 		   !ensure(log_, d.bin_tmp, tb))
 			return false;
-		ray_bin = true;
+		sch.ray_bin = true;
 	}
-	FgBatch fgb{};
-	auto fgPrepare = [&]() -> bool {
-		const int ns = S.fg_pass_samples > 0 ? S.fg_pass_samples : std::max(1, S.fg_samples);
-		const int nt = std::max(0, S.fg_bounces) + 1;
-		const size_t per_pos = (size_t)R * (size_t)ns * (16 + 48 + 16 * (size_t)nt);
-		size_t cap_max = std::max<size_t>(1, ((size_t)6 << 30) / per_pos);
-		if(const char *e = getenv("YAFARAY_AMD_FG_BATCH"); e && atoi(e) > 0) cap_max = std::min(cap_max, (size_t)atoi(e));   // tests: several batches
-		const size_t nb = ((size_t)S.cap_a + cap_max - 1) / cap_max;
-		const size_t seg_cap = std::max<size_t>(1, ((size_t)S.cap_a + nb - 1) / std::max<size_t>(1, nb));
-		const size_t paths = (size_t)R * seg_cap * (size_t)ns;
-		if(!ensure(log_, d.fg_terms, paths * 16) || !ensure(log_, d.fg_longs, paths * 48) || !ensure(log_, d.fg_long_terms, paths * 16 * (size_t)nt) ||
-		   !ensure(log_, d.fg_long_count, (size_t)R * 4))
-			return false;
-		fgb = FgBatch{0u, (uint32_t)seg_cap, ns, nt, (float4 *)d.fg_terms.p, (float4 *)d.fg_longs.p, (float4 *)d.fg_long_terms.p,
-		              (uint32_t *)d.fg_long_count.p, (uint32_t)(seg_cap * (size_t)ns)};
-		return true;
-	};
+	return true;
+}
+
+// ---- the segments' counters and the per-workgroup statistics ----
+bool GpuRenderer::Run::setupCounters()
+{
 	if(!ensure(log_, d.counters, 2 * 4 * R * sizeof(uint32_t))) return false;
 	// two ranges of trace_grid records: [0, trace_grid) for every launch of the render's ordered sequence, and
 	// [trace_grid, 2 trace_grid) for a shadow part that runs beside the closest part (below); summed on the host
 	if(!ensure(log_, d.stats, sizeof(DevStats) * 2 * (size_t)d.trace_grid)) return false;
 	HIPCHECK(hipMemsetAsync(d.counters.p, 0, 2 * 4 * R * sizeof(uint32_t), d.stream));
 	HIPCHECK(hipMemsetAsync(d.stats.p, 0, sizeof(DevStats) * 2 * (size_t)d.trace_grid, d.stream));
-	DevCounters cnt[2];
 	for(int q = 0; q < 2; ++q)
 	{
 		uint32_t *base_q = (uint32_t *)d.counters.p + (size_t)q * 4 * R;
@@ -2358,16 +2514,24 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		cnt[q].n_nee = base_q + 2 * R;
 		cnt[q].n_gather = base_q + 3 * R;
 	}
-	DevStats *dstats = (DevStats *)d.stats.p;
+	dstats = (DevStats *)d.stats.p;
 	S.stats = dstats;
+	run_stats = dstats;
+	return true;
+}
+
+// Which launch sequence the render runs: every decision taken once, before the first wavefront launch, with the
+// environment variables that override it (the gather's and the ray binning's are read by the setup steps that
+// allocate for them, before this), and the DevScene switches that tests set.
+bool GpuRenderer::Run::decideSchedule()
+{
 	// Opt-in YAFARAY_AMD_NEE_TRACE=1: k_nee traces its shadow rays in place for LDS-resident scenes
 	// (kernels.hip k_nee<.., TR>) when the whole stack bound fits LDS.  Measured on C2: k_trace
 	// 26.9 -> 18.2 ms per frame but k_nee 15.1 -> 29.4 ms (the traversal at k_nee's 4 waves / SIMD
 	// instead of k_trace's 8), frame 72.6 -> 79.0 ms — so the shadow rays stay queued for k_trace.
-	int nee_trace_stack = 0;
 	{
 		const char *ne = std::getenv("YAFARAY_AMD_NEE_TRACE");
-		if(yafamd_experiments() && ne && std::string(ne) == "1" && d.lds_stack >= d.stack_depth) nee_trace_stack = d.lds_stack;
+		if(yafamd_experiments() && ne && std::string(ne) == "1" && d.lds_stack >= d.stack_depth) sch.nee_trace_stack = d.lds_stack;
 	}
 	// The overlapped schedule (YAFARAY_AMD_OVERLAP): the closest rays of iteration it + 1 depend
 	// on k_shade(it) only, so they are traced on the side stream while k_nee(it) fills the shadow queue on the
@@ -2386,14 +2550,16 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 	// beside each other, and halving their k_nee grids only costs there (8 members on one GPU: 63.5 -> 68.3 ms),
 	// so they default to the serial schedule.  YAFARAY_AMD_OVERLAP=0 / 1 decides for every render; the grid
 	// variables are for sweeps.
-	bool overlap = rp.device_sharers <= 1;
-	int ov_nee_grid = std::max(1, (int)S.n_seg / 2), ov_trace_grid = std::max((int)S.n_seg, std::min(2 * (int)S.n_seg, d.trace_grid));
-	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP"); e && *e) overlap = *e != '0';
-	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_NEE_GRID"); e && atoi(e) > 0) ov_nee_grid = atoi(e);
+	sch.overlap = rp.device_sharers <= 1;
+	sch.ov_nee_grid = std::max(1, (int)S.n_seg / 2);
+	sch.ov_trace_grid = std::max((int)S.n_seg, std::min(2 * (int)S.n_seg, d.trace_grid));
+	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP"); e && *e) sch.overlap = *e != '0';
+	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_NEE_GRID"); e && atoi(e) > 0) sch.ov_nee_grid = atoi(e);
 	// (k_trace's grid is a multiple of n_seg: segLoop)
 	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_TRACE_GRID"); e && atoi(e) > 0)
-		ov_trace_grid = (int)S.n_seg * std::max(1, std::min(atoi(e), d.trace_grid) / (int)S.n_seg);
-	overlap = overlap && S.scene_in_lds && !S.ray_sort && !S.brute && !ray_bin && !S.tree && !S.tr_shad && !S.has_attr && nee_trace_stack == 0;
+		sch.ov_trace_grid = (int)S.n_seg * std::max(1, std::min(atoi(e), d.trace_grid) / (int)S.n_seg);
+	sch.overlap = sch.overlap && S.scene_in_lds && !S.ray_sort && !S.brute && !sch.ray_bin && !S.tree && !S.tr_shad && !S.has_attr &&
+	              sch.nee_trace_stack == 0;
 	// The shadow part beside the closest part (YAFARAY_AMD_OVERLAP_SHADOW): the shadow rays of iteration it + 1
 	// depend on k_nee(it) only, and share nothing with the closest part on the side stream (sh_o / sh_d /
 	// n_shadow -> P.occ against ray_o / ray_d / n_active -> hit_t / hit_prim).  So their k_trace follows k_nee(it)
@@ -2406,20 +2572,19 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 	// shadow grid or a larger k_nee share measured slower, the closest part on 4096 equal within the spread).
 	// YAFARAY_AMD_OVERLAP_SHADOW=0 keeps the shadow part behind the join; _SHADOW_GRID is its grid (a multiple of
 	// n_seg, at most trace_grid).
-	bool ov_shadow = true;
-	int ov_shadow_grid = d.trace_grid;
-	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_SHADOW"); e && *e) ov_shadow = *e != '0';
+	sch.ov_shadow = true;
+	sch.ov_shadow_grid = d.trace_grid;
+	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_SHADOW"); e && *e) sch.ov_shadow = *e != '0';
 	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_SHADOW_GRID"); e && atoi(e) > 0)
-		ov_shadow_grid = (int)S.n_seg * std::max(1, std::min(atoi(e), d.trace_grid) / (int)S.n_seg);
-	ov_shadow = ov_shadow && overlap && d.spill.p == nullptr;
+		sch.ov_shadow_grid = (int)S.n_seg * std::max(1, std::min(atoi(e), d.trace_grid) / (int)S.n_seg);
+	sch.ov_shadow = sch.ov_shadow && sch.overlap && d.spill.p == nullptr;
 	// k_trace's deferred leaf tests (upload() decided the capacity): every launch of the render, full or part,
 	// timed or with statistics, runs the same traversal.  Iteration 0 keeps the interleaved loop under either
 	// schedule: the coherent camera rays of a wave hit the same leaves at the same visits, so the lists only add
 	// their bookkeeping (C2: 2.0 -> 2.4 ms for that launch, profiles/c2_trace_deferred.md);
 	// YAFARAY_AMD_TRACE_DEFER_IT0=1 uses the lists there too (A/B)
 	d.Q[0].trace_defer = d.Q[1].trace_defer = traceDeferCap(d.trace_defer);
-	bool defer_it0 = false;
-	if(const char *e = std::getenv("YAFARAY_AMD_TRACE_DEFER_IT0"); e && *e) defer_it0 = *e != '0';
+	if(const char *e = std::getenv("YAFARAY_AMD_TRACE_DEFER_IT0"); e && *e) sch.defer_it0 = *e != '0';
 	// The megakernel (k_path, kernels.hip; opt-in YAFARAY_AMD_PATH=mega) for scenes whose BVH, stack
 	// and tables live in LDS and need none of the wavefront-only stages (EXT shading, transparent
 	// shadows, photon maps, AO): one lane per sample, the same functions in the same order, the film
@@ -2429,8 +2594,8 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 	// render's running counter: every pass runs a count run first (lpcBases).  A specular recursion tree
 	// (several integrate() nodes per sample) and caller-side shards (no exchange of the other rows'
 	// counts) keep pickLight; YAFARAY_AMD_LIGHT_PICK=hash forces it.
-	bool lpc_on = S.integrator == INT_PATH && S.n_lights > 1 && !S.tree && (rp.shard_world <= 1 || group_render);
-	if(const char *lp = std::getenv("YAFARAY_AMD_LIGHT_PICK"); lp && std::string(lp) == "hash") lpc_on = false;
+	sch.lpc_on = S.integrator == INT_PATH && S.n_lights > 1 && !S.tree && (rp.shard_world <= 1 || group_render);
+	if(const char *lp = std::getenv("YAFARAY_AMD_LIGHT_PICK"); lp && std::string(lp) == "hash") sch.lpc_on = false;
 	lpc_carry_ = 0;
 	S.lpc = nullptr;
 	S.lpc_mode = 0;
@@ -2447,191 +2612,217 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 	// pr record: k_camera writes none then), iteration 1 the first-segment kernel and the later ones the bounce
 	// kernel.  Decided once per render, for k_camera and every k_shade alike; YAFARAY_AMD_SHADE_STAGES=0 keeps the
 	// kernel that reads the stage from the record (tests, A/B).
-	bool shade_stages = !lpc_on && yafamd_shade_stages_for(&S) != 0;
-	if(const char *e = std::getenv("YAFARAY_AMD_SHADE_STAGES"); e && *e == '0') shade_stages = false;
-	int path_grid = 0;
-	if(!lpc_on)
+	sch.shade_stages = !sch.lpc_on && yafamd_shade_stages_for(&S) != 0;
+	if(const char *e = std::getenv("YAFARAY_AMD_SHADE_STAGES"); e && *e == '0') sch.shade_stages = false;
+	if(!sch.lpc_on)
 	{
 		const char *pe = std::getenv("YAFARAY_AMD_PATH");
 		const bool on = yafamd_experiments() && pe && std::string(pe) == "mega";
 		if(on && yafamd_path_eligible(&S, d.lds_stack, d.lds_stack < d.stack_depth ? 1 : 0))
 		{
-			path_grid = std::min(d.trace_grid, d.n_cu * std::max(1, yafamd_path_blocks_per_cu(&S, d.lds_stack)));
-			if(const char *e = getenv("YAFARAY_AMD_PATH_GRID")) path_grid = std::min(d.trace_grid, std::max(1, atoi(e)));
+			sch.path_grid = std::min(d.trace_grid, d.n_cu * std::max(1, yafamd_path_blocks_per_cu(&S, d.lds_stack)));
+			if(const char *e = getenv("YAFARAY_AMD_PATH_GRID")) sch.path_grid = std::min(d.trace_grid, std::max(1, atoi(e)));
 			if(!ensure(log_, d.path_next, 16)) return false;
 		}
 	}
 	const int n_paths = std::max(1, S.path_samples);
-	const int iters = (S.integrator == INT_PATH) ? 2 + n_paths * (S.bounces + 2) : 3;
+	sch.iters = (S.integrator == INT_PATH) ? 2 + n_paths * (S.bounces + 2) : 3;
+	return true;
+}
 
-	// ---- events ----
-	auto ensureEvents = [&](size_t need) -> bool {
-		while(d.ev_pool.size() < need)
-		{
-			hipEvent_t e;
-			HIPCHECK(hipEventCreate(&e));
-			d.ev_pool.push_back(e);
-		}
-		return true;
-	};
-	if(!ensureEvents(2)) return false;
+// ---- events: the render's clock starts here ----
+bool GpuRenderer::Run::startClock()
+{
+	while(d.ev_pool.size() < 2)
+	{
+		hipEvent_t e;
+		HIPCHECK(hipEventCreate(&e));
+		d.ev_pool.push_back(e);
+	}
 	HIPCHECK(hipEventRecord(d.ev_pool[0], d.stream));
-	// one pass: `n_total` camera samples (the jobs' enumeration, or S.plist x S.spp) through the wavefront
-	// one wavefront pass over the active list started by k_camera / k_spawn
-	DevStats *run_stats = dstats;   // the light-pick count runs count into their own statistics
-	bool shade_staged = false;      // some k_shade launch was stage-specialised: its guard words are read after the render
-	auto iterate =[&](uint64_t base) -> bool {
-		int cur = 0;
-		// a light-pick count run (S.lpc_mode 1) follows the paths only: no estimates, no shadow rays
-		const bool count_run = S.lpc_mode == 1;
-		// the overlapped schedule: this iteration's closest rays were traced on the side stream beside the
-		// previous iteration's k_nee; the render stream has waited for them (ev_join), or — with the early shadow
-		// part — waits right after this iteration's shadow launch
-		bool closest_done = false;
-		for(int it = 0; it < iters; ++it)
+	return true;
+}
+
+// The early shadow part: the side stream's closest part of this iteration is still running, so the shadow part
+// goes beside it (counting into the second range of the statistics), then the render stream joins the side stream
+// (eligible renders only: no ray binning before it, no k_tshadow / k_surface after it, no spill column)
+bool GpuRenderer::Run::launchShadowBesideClosest(const DevQueues &qc, int cur)
+{
+	SideSync side{d.side};   // a failed launch: leave no side-stream work behind
+	PROF(KK_TRACE, yafamd_launch_trace(&S, &qc, &cnt[cur], &d.P[cur], run_stats + d.trace_grid, d.lds_stack, nullptr, sch.ov_shadow_grid,
+	                                    d.stream));
+	HIPCHECK(hipStreamWaitEvent(d.stream, d.ev_join, 0));
+	side.ok = true;
+	return true;
+}
+
+// k_shade(it) is queued: the next iteration's closest rays go to the side stream, k_nee(it)
+// beside them to the render stream, which then waits for the side stream — so nothing of
+// the side stream is pending when this iteration's launches end (chunk buffers, the next
+// pass and the render's final synchronisation see one stream, as before).  With the early shadow
+// part that wait moves behind the next iteration's shadow launch: iterate() takes this branch only
+// with a next iteration, whose k_trace launch is unconditional, so the join still happens
+// inside iterate(), ahead of that iteration's k_shade
+bool GpuRenderer::Run::launchNeeBesideNextClosest(int cur)
+{
+	DevQueues qn = d.Q[cur ^ 1];
+	qn.ray_tt = nullptr;
+	qn.tmin_dflt = S.ray_min_dist;
+	qn.perm = nullptr;
+	qn.trace_part = TRACE_CLOSEST;
+	DevQueues qnee = d.Q[cur ^ 1];
+	qnee.nee_grid = sch.ov_nee_grid;
+	HIPCHECK(hipEventRecord(d.ev_fork, d.stream));
+	HIPCHECK(hipStreamWaitEvent(d.side, d.ev_fork, 0));
+	SideSync side{d.side};   // a failed launch: leave no side-stream work behind
+	PROF_ON(KK_TRACE, d.side, yafamd_launch_trace(&S, &qn, &cnt[cur ^ 1], &d.P[cur ^ 1], run_stats, d.lds_stack, (int *)d.spill.p,
+	                                              sch.ov_trace_grid, d.side));
+	HIPCHECK(hipEventRecord(d.ev_join, d.side));
+	PROF(KK_NEE, yafamd_launch_nee(&S, &d.N, &d.P[cur ^ 1], &qnee, &cnt[cur ^ 1], sch.nee_trace_stack, d.stream));
+	// (the early shadow part: the next iteration joins, after its shadow launch)
+	if(!sch.ov_shadow) HIPCHECK(hipStreamWaitEvent(d.stream, d.ev_join, 0));
+	side.ok = true;
+	return true;
+}
+
+// the batch buffers of the per-path final gathering for this pass's S.fg_pass_samples (called per iteration: the
+// count changes per pass, and ensure() keeps buffers that are large enough)
+bool GpuRenderer::Run::fgPrepare()
+{
+	const int ns = S.fg_pass_samples > 0 ? S.fg_pass_samples : std::max(1, S.fg_samples);
+	const int nt = std::max(0, S.fg_bounces) + 1;
+	const size_t per_pos = (size_t)R * (size_t)ns * (16 + 48 + 16 * (size_t)nt);
+	size_t cap_max = std::max<size_t>(1, ((size_t)6 << 30) / per_pos);
+	if(const char *e = getenv("YAFARAY_AMD_FG_BATCH"); e && atoi(e) > 0) cap_max = std::min(cap_max, (size_t)atoi(e));   // tests: several batches
+	const size_t nb = ((size_t)S.cap_a + cap_max - 1) / cap_max;
+	const size_t seg_cap = std::max<size_t>(1, ((size_t)S.cap_a + nb - 1) / std::max<size_t>(1, nb));
+	const size_t paths = (size_t)R * seg_cap * (size_t)ns;
+	if(!ensure(log_, d.fg_terms, paths * 16) || !ensure(log_, d.fg_longs, paths * 48) || !ensure(log_, d.fg_long_terms, paths * 16 * (size_t)nt) ||
+	   !ensure(log_, d.fg_long_count, (size_t)R * 4))
+		return false;
+	fgb = FgBatch{0u, (uint32_t)seg_cap, ns, nt, (float4 *)d.fg_terms.p, (float4 *)d.fg_longs.p, (float4 *)d.fg_long_terms.p,
+	              (uint32_t *)d.fg_long_count.p, (uint32_t)(seg_cap * (size_t)ns)};
+	return true;
+}
+
+// the photon-map estimates of the requests k_shade just queued (queue cur ^ 1): final gathering adds its
+// estimate to the requests' colour before k_gather ends them
+bool GpuRenderer::Run::launchGathers(int cur, uint64_t base)
+{
+	if(S.fg_on && sch.fg_paths)
+	{
+		if(!fgPrepare()) return false;
+		// one lane per gather path, in batches of request positions (every segment's [j0, j0 + seg_cap))
+		for(uint32_t j0 = 0; j0 < S.cap_a; j0 += fgb.seg_cap)
 		{
-			// the first iteration's closest rays (camera / spawned, queue 0) carry their own (tmin, tmax);
-			// k_shade's bounce rays all have (ray_min_dist, infinite)
-			DevQueues qc = d.Q[cur];
-			// (camera rays with the default clip planes all have (0, unbounded): k_camera writes no ray_tt)
-			if(it != 0 || (S.cur_level == 0 && !S.cam.ray_tt)) qc.ray_tt = nullptr;
-			qc.tmin_dflt = it == 0 ? 0.f : S.ray_min_dist;
-			qc.perm = nullptr;
-			qc.trace_part = closest_done ? TRACE_SHADOW : TRACE_BOTH;
-			if(it == 0 && !defer_it0) qc.trace_defer = 0;
-			// the side stream's closest part is still running: the shadow part goes beside it, then the join
-			const bool join_pending = closest_done && ov_shadow;
-			closest_done = false;
-			if(ray_bin && it >= 1 && !count_run)
+			FgBatch B = fgb;
+			B.j0 = j0;
+			HIPCHECK(hipMemsetAsync(fgb.long_count, 0, (size_t)S.n_seg * 4, d.stream));
+			PROF(KK_FG, yafamd_launch_fg_paths(&S, &d.G, &cnt[cur ^ 1], d.lds_stack, (int *)d.spill.p, d.trace_grid, &B, d.stream));
+		}
+	}
+	else if(S.fg_on)
+		PROF(KK_FG, yafamd_launch_fg(&S, &d.G, &cnt[cur ^ 1], d.lds_stack, (int *)d.spill.p, d.trace_grid, (float2 *)d.fg_ts.p, d.stream));
+	if(sch.walk_gather)
+		for(uint32_t j0 = 0; j0 < S.cap_a; j0 += glog.seg_cap)
+		{
+			GatherLogDesc L = glog;
+			L.j0 = j0;
+			PROF(KK_GATHER_WALK, yafamd_launch_gather_walk(&S, &d.G, &cnt[cur ^ 1], &L, d.stream));
+			PROF(KK_GATHER, yafamd_launch_gather(&S, &d.G, &cnt[cur ^ 1], (float4 *)d.samples.p, (const DevJob *)d.jobs.p, n_jobs, base,
+			                                     &L, d.stream));
+		}
+	else
+		PROF(KK_GATHER, yafamd_launch_gather(&S, &d.G, &cnt[cur ^ 1], (float4 *)d.samples.p, (const DevJob *)d.jobs.p, n_jobs, base,
+		                                     nullptr, d.stream));
+	return true;
+}
+
+// one wavefront pass over the active list started by k_camera / k_spawn
+bool GpuRenderer::Run::iterate(uint64_t base)
+{
+	int cur = 0;
+	// a light-pick count run (S.lpc_mode 1) follows the paths only: no estimates, no shadow rays
+	const bool count_run = S.lpc_mode == 1;
+	// the overlapped schedule: this iteration's closest rays were traced on the side stream beside the
+	// previous iteration's k_nee; the render stream has waited for them (ev_join), or — with the early shadow
+	// part — waits right after this iteration's shadow launch
+	bool closest_done = false;
+	for(int it = 0; it < sch.iters; ++it)
+	{
+		// the first iteration's closest rays (camera / spawned, queue 0) carry their own (tmin, tmax);
+		// k_shade's bounce rays all have (ray_min_dist, infinite)
+		DevQueues qc = d.Q[cur];
+		// (camera rays with the default clip planes all have (0, unbounded): k_camera writes no ray_tt)
+		if(it != 0 || (S.cur_level == 0 && !S.cam.ray_tt)) qc.ray_tt = nullptr;
+		qc.tmin_dflt = it == 0 ? 0.f : S.ray_min_dist;
+		qc.perm = nullptr;
+		qc.trace_part = closest_done ? TRACE_SHADOW : TRACE_BOTH;
+		if(it == 0 && !sch.defer_it0) qc.trace_defer = 0;
+		// the side stream's closest part is still running: the shadow part goes beside it, then the join
+		const bool join_pending = closest_done && sch.ov_shadow;
+		closest_done = false;
+		if(sch.ray_bin && it >= 1 && !count_run)
+		{
+			// the bounce rays ordered by direction octant + origin (camera rays are coherent already)
+			size_t tb = d.bin_tmp.bytes;
+			HIPCHECK(yafamd_ray_bin(&qc, &cnt[cur], S.n_seg, S.cap_a, d.scene_lo, d.scene_hi, (uint32_t *)d.bin_keys.p, (uint32_t *)d.bin_keys2.p,
+			                        (uint32_t *)d.bin_iota.p, (uint32_t *)d.bin_perm.p, d.bin_tmp.p, &tb, d.stream));
+			qc.perm = (const uint32_t *)d.bin_perm.p;
+		}
+		if(join_pending)
+		{
+			if(!launchShadowBesideClosest(qc, cur)) return false;
+		}
+		else
+			PROF(KK_TRACE, yafamd_launch_trace(&S, &qc, &cnt[cur], &d.P[cur], run_stats, d.lds_stack, (int *)d.spill.p,
+			                                    S.tr_shad ? d.trace_grid_bvh4 : d.trace_grid, d.stream));
+		// material-shade dispatch for textured / smooth scenes: surface attributes + shader nodes
+		// of every hit, before k_shade reads them
+		// transparent shadows: filter colours of the transparent surfaces the shadow rays crossed
+		if(S.tr_shad && !count_run) PROF(KK_TSHADOW, yafamd_launch_tshadow(&S, &qc, &cnt[cur], &d.P[cur], d.stream));
+		if(S.has_attr) PROF(KK_SURFACE, yafamd_launch_surface(&S, &qc, &cnt[cur], d.stream));
+		// the deferred light pick's record slots of this iteration (one per active entry)
+		if(S.lpc_mode == 3)
+			HIPCHECK(yafamd_dfr_segoff(&cnt[cur], S.n_seg, (uint32_t *)d.dfr_segoff.p, (uint32_t *)d.dfr_misc.p, S.dfr_cap,
+			                           (uint32_t *)d.dfr_misc.p + 1, (uint32_t *)d.dfr_its.p, d.stream));
+		// (shade_stages implies no recursion tree, so S.cur_level == 0, and no light-pick run, so S.lpc_mode == 0)
+		const int stage_it = (sch.shade_stages && S.cur_level == 0 && S.lpc_mode == 0 && !S.tree) ? it : -1;
+		PROF(KK_SHADE, yafamd_launch_shade(&S, &d.P[cur], &d.P[cur ^ 1], &qc, &d.Q[cur ^ 1], &d.N, &d.G, &cnt[cur], &cnt[cur ^ 1],
+		                             (float4 *)d.samples.p, (const DevJob *)d.jobs.p, n_jobs, base, stage_it, d.stream));
+		if(stage_it >= 0)
+		{
+			shade_staged = true;
+			if(rp.profile) ++ktimes_.launches[KK_SHADE_STAGED];
+		}
+
+		// photon-map estimates of the finished diffuse first hits: the direct-lighting pipeline
+		// (photon mapping, DirectLight) connects its NEE in iteration 1 and finishes there; path
+		// tracing finishes paths in any iteration
+		const bool dl_pipeline = S.integrator != INT_PATH;
+		// (show_map: the camera hits finish in iteration 0, with their nearest-photon requests)
+		if(S.gather_on && !count_run && (!dl_pipeline || it == 1 || (S.show_map && it == 0)) && !launchGathers(cur, base)) return false;
+		// NEE requests (none in iteration 1 of photon mapping, whose entries all finish there)
+		if(!yafamd_shade_fused_for(&S) && !(S.integrator == INT_PHOTON && it == 1) && !count_run)
+		{
+			if(sch.overlap && S.lpc_mode == 0 && !S.gather_on && it + 1 < sch.iters)
 			{
-				// the bounce rays ordered by direction octant + origin (camera rays are coherent already)
-				size_t tb = d.bin_tmp.bytes;
-				HIPCHECK(yafamd_ray_bin(&qc, &cnt[cur], S.n_seg, S.cap_a, d.scene_lo, d.scene_hi, (uint32_t *)d.bin_keys.p, (uint32_t *)d.bin_keys2.p,
-				                        (uint32_t *)d.bin_iota.p, (uint32_t *)d.bin_perm.p, d.bin_tmp.p, &tb, d.stream));
-				qc.perm = (const uint32_t *)d.bin_perm.p;
-			}
-			if(join_pending)
-			{
-				// (eligible renders only: no ray binning above, no k_tshadow / k_surface below, no spill column)
-				bool ok = [&]() -> bool {
-					PROF(KK_TRACE, yafamd_launch_trace(&S, &qc, &cnt[cur], &d.P[cur], run_stats + d.trace_grid, d.lds_stack, nullptr, ov_shadow_grid,
-					                                    d.stream));
-					HIPCHECK(hipStreamWaitEvent(d.stream, d.ev_join, 0));
-					return true;
-				}();
-				if(!ok)
-				{
-					(void)hipStreamSynchronize(d.side);   // a failed launch: leave no side-stream work behind
-					return false;
-				}
+				if(!launchNeeBesideNextClosest(cur)) return false;
+				closest_done = true;
 			}
 			else
-				PROF(KK_TRACE, yafamd_launch_trace(&S, &qc, &cnt[cur], &d.P[cur], run_stats, d.lds_stack, (int *)d.spill.p,
-				                                    S.tr_shad ? d.trace_grid_bvh4 : d.trace_grid, d.stream));
-			// material-shade dispatch for textured / smooth scenes: surface attributes + shader nodes
-			// of every hit, before k_shade reads them
-			// transparent shadows: filter colours of the transparent surfaces the shadow rays crossed
-			if(S.tr_shad && !count_run) PROF(KK_TSHADOW, yafamd_launch_tshadow(&S, &qc, &cnt[cur], &d.P[cur], d.stream));
-			if(S.has_attr) PROF(KK_SURFACE, yafamd_launch_surface(&S, &qc, &cnt[cur], d.stream));
-			// the deferred light pick's record slots of this iteration (one per active entry)
-			if(S.lpc_mode == 3)
-				HIPCHECK(yafamd_dfr_segoff(&cnt[cur], S.n_seg, (uint32_t *)d.dfr_segoff.p, (uint32_t *)d.dfr_misc.p, S.dfr_cap,
-				                           (uint32_t *)d.dfr_misc.p + 1, (uint32_t *)d.dfr_its.p, d.stream));
-			// (shade_stages implies no recursion tree, so S.cur_level == 0, and no light-pick run, so S.lpc_mode == 0)
-			const int stage_it = (shade_stages && S.cur_level == 0 && S.lpc_mode == 0 && !S.tree) ? it : -1;
-			PROF(KK_SHADE, yafamd_launch_shade(&S, &d.P[cur], &d.P[cur ^ 1], &qc, &d.Q[cur ^ 1], &d.N, &d.G, &cnt[cur], &cnt[cur ^ 1],
-			                             (float4 *)d.samples.p, (const DevJob *)d.jobs.p, n_jobs, base, stage_it, d.stream));
-			if(stage_it >= 0)
-			{
-				shade_staged = true;
-				if(rp.profile) ++ktimes_.launches[KK_SHADE_STAGED];
-			}
-
-			// photon-map estimates of the finished diffuse first hits: the direct-lighting pipeline
-			// (photon mapping, DirectLight) connects its NEE in iteration 1 and finishes there; path
-			// tracing finishes paths in any iteration
-			const bool dl_pipeline = S.integrator != INT_PATH;
-			// (show_map: the camera hits finish in iteration 0, with their nearest-photon requests)
-			if(S.gather_on && !count_run && (!dl_pipeline || it == 1 || (S.show_map && it == 0)))
-			{
-				// final gathering adds its estimate to the requests' colour before k_gather ends them
-				if(S.fg_on && fg_paths)
-				{
-					if(!fgPrepare()) return false;
-					// one lane per gather path, in batches of request positions (every segment's [j0, j0 + seg_cap))
-					for(uint32_t j0 = 0; j0 < S.cap_a; j0 += fgb.seg_cap)
-					{
-						FgBatch B = fgb;
-						B.j0 = j0;
-						HIPCHECK(hipMemsetAsync(fgb.long_count, 0, (size_t)S.n_seg * 4, d.stream));
-						PROF(KK_FG, yafamd_launch_fg_paths(&S, &d.G, &cnt[cur ^ 1], d.lds_stack, (int *)d.spill.p, d.trace_grid, &B, d.stream));
-					}
-				}
-				else if(S.fg_on)
-					PROF(KK_FG, yafamd_launch_fg(&S, &d.G, &cnt[cur ^ 1], d.lds_stack, (int *)d.spill.p, d.trace_grid, (float2 *)d.fg_ts.p, d.stream));
-				if(walk_gather)
-					for(uint32_t j0 = 0; j0 < S.cap_a; j0 += glog.seg_cap)
-					{
-						GatherLogDesc L = glog;
-						L.j0 = j0;
-						PROF(KK_GATHER_WALK, yafamd_launch_gather_walk(&S, &d.G, &cnt[cur ^ 1], &L, d.stream));
-						PROF(KK_GATHER, yafamd_launch_gather(&S, &d.G, &cnt[cur ^ 1], (float4 *)d.samples.p, (const DevJob *)d.jobs.p, n_jobs, base,
-						                                     &L, d.stream));
-					}
-				else
-					PROF(KK_GATHER, yafamd_launch_gather(&S, &d.G, &cnt[cur ^ 1], (float4 *)d.samples.p, (const DevJob *)d.jobs.p, n_jobs, base,
-					                                     nullptr, d.stream));
-			}
-			// NEE requests (none in iteration 1 of photon mapping, whose entries all finish there)
-			if(!yafamd_shade_fused_for(&S) && !(S.integrator == INT_PHOTON && it == 1) && !count_run)
-			{
-				if(overlap && S.lpc_mode == 0 && !S.gather_on && it + 1 < iters)
-				{
-					// k_shade(it) is queued: the next iteration's closest rays go to the side stream, k_nee(it)
-					// beside them to the render stream, which then waits for the side stream — so nothing of
-					// the side stream is pending when this iteration's launches end (chunk buffers, the next
-					// pass and the render's final synchronisation see one stream, as before).  With the early shadow
-					// part that wait moves behind the next iteration's shadow launch: this branch is only taken
-					// with a next iteration, whose k_trace launch is unconditional, so the join still happens
-					// inside iterate(), ahead of that iteration's k_shade
-					DevQueues qn = d.Q[cur ^ 1];
-					qn.ray_tt = nullptr;
-					qn.tmin_dflt = S.ray_min_dist;
-					qn.perm = nullptr;
-					qn.trace_part = TRACE_CLOSEST;
-					DevQueues qnee = d.Q[cur ^ 1];
-					qnee.nee_grid = ov_nee_grid;
-					HIPCHECK(hipEventRecord(d.ev_fork, d.stream));
-					HIPCHECK(hipStreamWaitEvent(d.side, d.ev_fork, 0));
-					bool ok = [&]() -> bool {
-						PROF_ON(KK_TRACE, d.side, yafamd_launch_trace(&S, &qn, &cnt[cur ^ 1], &d.P[cur ^ 1], run_stats, d.lds_stack, (int *)d.spill.p,
-						                                              ov_trace_grid, d.side));
-						HIPCHECK(hipEventRecord(d.ev_join, d.side));
-						PROF(KK_NEE, yafamd_launch_nee(&S, &d.N, &d.P[cur ^ 1], &qnee, &cnt[cur ^ 1], nee_trace_stack, d.stream));
-						// (the early shadow part: the next iteration joins, after its shadow launch)
-						if(!ov_shadow) HIPCHECK(hipStreamWaitEvent(d.stream, d.ev_join, 0));
-						return true;
-					}();
-					if(!ok)
-					{
-						(void)hipStreamSynchronize(d.side);   // a failed launch: leave no side-stream work behind
-						return false;
-					}
-					closest_done = true;
-				}
-				else
-					PROF(KK_NEE, yafamd_launch_nee(&S, &d.N, &d.P[cur ^ 1], &d.Q[cur ^ 1], &cnt[cur ^ 1], nee_trace_stack, d.stream));
-			}
-			// (non-EXT k_shade runs the NEE itself: FUSED)
-			cur ^= 1;
+				PROF(KK_NEE, yafamd_launch_nee(&S, &d.N, &d.P[cur ^ 1], &d.Q[cur ^ 1], &cnt[cur ^ 1], sch.nee_trace_stack, d.stream));
 		}
-		return true;
-	};
-	bool tree_overflow_logged = false;
-	// one pass: `n_total` camera samples (the jobs' enumeration, or S.plist x S.spp) through the wavefront;
-	// `done` = samples of the chunks that ran (< n_total only when the render was canceled)
-	uint64_t done = 0;
-	auto runSamples = [&](uint64_t n_total) -> bool {
+		// (non-EXT k_shade runs the NEE itself: FUSED)
+		cur ^= 1;
+	}
+	return true;
+}
+
+// one pass: `n_total` camera samples (the jobs' enumeration, or S.plist x S.spp) through the wavefront;
+// `done` = samples of the chunks that ran (< n_total only when the render was canceled)
+bool GpuRenderer::Run::runSamples(uint64_t n_total)
+{
 	done = 0;
 	for(uint64_t base = 0; base < n_total; base += M, done = std::min(base, n_total))
 	{
@@ -2643,230 +2834,265 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 			rp.on_chunk(base, n_total);
 			if(canceled && *canceled) break;
 		}
-		if(path_grid > 0)
+		if(sch.path_grid > 0)
 		{
 			HIPCHECK(hipMemsetAsync(d.path_next.p, 0, 4, d.stream));
 			PROF(KK_PATH, yafamd_launch_path(&S, (float4 *)d.samples.p, (const DevJob *)d.jobs.p, n_jobs, base, (uint32_t)n, (uint32_t *)d.path_next.p,
-			                                 d.lds_stack, path_grid, d.stream));
+			                                 d.lds_stack, sch.path_grid, d.stream));
 			continue;
 		}
 		if(S.tree) HIPCHECK(hipMemsetAsync(d.spawn_count.p, 0, 16, d.stream));
 		S.cur_level = 0;
-		PROF(KK_CAMERA, yafamd_launch_camera(&S, &d.P[0], &d.Q[0], &cnt[0], (const DevJob *)d.jobs.p, n_jobs, base, n, shade_stages ? 0 : 1, d.stream));
+		PROF(KK_CAMERA, yafamd_launch_camera(&S, &d.P[0], &d.Q[0], &cnt[0], (const DevJob *)d.jobs.p, n_jobs, base, n, sch.shade_stages ? 0 : 1, d.stream));
 		if(!iterate(base)) return false;
-		if(!S.tree) continue;
-		// recursiveRaytrace levels: the nodes the last pass spawned are the next pass's active list
-		std::vector<std::pair<uint32_t, uint32_t>> levels;
-		uint32_t done = 0;
-		for(int level = 1;; ++level)
-		{
-			uint32_t hc[2] = {0, 0};
-			HIPCHECK(hipMemcpyAsync(hc, d.spawn_count.p, 8, hipMemcpyDeviceToHost, d.stream));
-			HIPCHECK(hipStreamSynchronize(d.stream));
-			if(hc[1] && !tree_overflow_logged)
-			{
-				log_.error("Integrator: the specular recursion tree exceeded its " + std::to_string(S.spawn_cap) + " node records; deeper rays dropped");
-				tree_overflow_logged = true;
-			}
-			const uint32_t total_spawned = std::min(hc[0], S.spawn_cap);
-			if(total_spawned <= done) break;
-			S.cur_level = level;
-			for(uint32_t sub = done; sub < total_spawned; sub += (uint32_t)M)
-			{
-				const int nn = (int)std::min<uint64_t>(M, total_spawned - sub);
-				PROF(KK_SPAWN, yafamd_launch_spawn(&S, &d.P[0], &d.Q[0], &cnt[0], sub, nn, d.stream));
-				if(!iterate(base)) return false;
-			}
-			levels.push_back({done, total_spawned});
-			done = total_spawned;
-		}
-		for(size_t k = levels.size(); k-- > 0;)
-			PROF(KK_COMBINE, yafamd_launch_combine(&S, S.node_base + levels[k].first, S.node_base + levels[k].second, 0, nullptr, nullptr, 0, 0, d.stream));
-		PROF(KK_COMBINE, yafamd_launch_combine(&S, 0, (uint32_t)n, 1, (float4 *)d.samples.p, (const DevJob *)d.jobs.p, n_jobs, base, d.stream));
-		S.cur_level = 0;
+		if(S.tree && !runTreeLevels(base, n)) return false;
 	}
 	return true;
-	};
-	// one pass's samples; with the one-thread light pick a count run first (the paths only: closest
-	// rays and shading, no estimates), then the counters' bases (lpcBases), then the render proper
-	int jy0 = H, jy1 = 0;
-	for(const DevJob &j : jobs)
+}
+
+// recursiveRaytrace levels of the chunk at `base` (`n` samples): the nodes the last pass spawned are the next
+// pass's active list; then the levels' colours combine upwards into the samples
+bool GpuRenderer::Run::runTreeLevels(uint64_t base, int n)
+{
+	std::vector<std::pair<uint32_t, uint32_t>> levels;
+	uint32_t spawned_done = 0;
+	for(int level = 1;; ++level)
 	{
-		jy0 = std::min(jy0, j.y0);
-		jy1 = std::max(jy1, j.y1);
+		uint32_t hc[2] = {0, 0};
+		HIPCHECK(hipMemcpyAsync(hc, d.spawn_count.p, 8, hipMemcpyDeviceToHost, d.stream));
+		HIPCHECK(hipStreamSynchronize(d.stream));
+		if(hc[1] && !tree_overflow_logged)
+		{
+			log_.error("Integrator: the specular recursion tree exceeded its " + std::to_string(S.spawn_cap) + " node records; deeper rays dropped");
+			tree_overflow_logged = true;
+		}
+		const uint32_t total_spawned = std::min(hc[0], S.spawn_cap);
+		if(total_spawned <= spawned_done) break;
+		S.cur_level = level;
+		for(uint32_t sub = spawned_done; sub < total_spawned; sub += (uint32_t)M)
+		{
+			const int nn = (int)std::min<uint64_t>(M, total_spawned - sub);
+			PROF(KK_SPAWN, yafamd_launch_spawn(&S, &d.P[0], &d.Q[0], &cnt[0], sub, nn, d.stream));
+			if(!iterate(base)) return false;
+		}
+		levels.push_back({spawned_done, total_spawned});
+		spawned_done = total_spawned;
 	}
-	auto runPass = [&](uint64_t n_total, int pass_spp) -> bool {
-		if(!lpc_on) return runSamples(n_total);
-		const size_t n_ctr = (size_t)W * H * (size_t)pass_spp;
-		// one 4-B counter per camera sample of the pass (8.5 GB at 1080p x 1024 spp): above a budget of a
-		// quarter of the device's free memory, or when the allocation fails, the pass falls back to the
-		// hashed pick (matched statistically) instead of failing the render
-		{
-			size_t free_b = 0, total_b = 0;
-			const bool have = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
-			bool fits = d.lpc.bytes >= n_ctr * 4 || (have && n_ctr * 4 <= (free_b + d.lpc.bytes) / 4);
-			if(const char *e = std::getenv("YAFARAY_AMD_LPC_MAX_MB"); e && *e) fits = fits && (n_ctr * 4 >> 20) < (size_t)std::max(0, atoi(e));
-			auto tryEnsure = [](Buf &b, size_t bytes) {
-				if(b.p && b.bytes >= bytes) return true;
-				b.release();
-				if(hipMalloc(&b.p, std::max<size_t>(bytes, 16)) != hipSuccess)
-				{
-					b.p = nullptr;
-					(void)hipGetLastError();
-					return false;
-				}
-				b.bytes = std::max<size_t>(bytes, 16);
-				return true;
-			};
-			bool can = fits && tryEnsure(d.lpc, n_ctr * 4) && tryEnsure(d.lpc_stats, sizeof(DevStats) * (size_t)d.trace_grid);
-			if(group_render)
-			{
-				// every member takes the same pick (the count run's bases are exchanged): fall back together
-				const int st = groupStatus(can ? 0 : 1);
-				if(st >= 2)
-				{
-					log_.error("GPU group: a member failed; render abandoned");
-					return false;
-				}
-				can = st == 0;
-			}
-			if(!can)
-			{
-				log_.warning("Integrator: the one-thread light-pick counters (" + std::to_string(n_ctr * 4 >> 20) +
-				             " MB) exceed the memory budget; this pass picks lights by sample hash");
-				return runSamples(n_total);
-			}
-		}
-		// the deferred pick (r06): the pass once with every addition to a path colour kept as a record, the
-		// lights picked from the counters' bases afterwards, the records folded in order — no count run.  A
-		// group render (collective bases) and scenes it does not serve keep the count run; so does a pass whose
-		// records overflow their budget (a third of the free memory), rendered again below
-		if(!group_render && yafamd_dfr_eligible(&S))
-		{
-			size_t free_b = 0, total_b = 0;
-			(void)hipMemGetInfo(&free_b, &total_b);
-			const size_t want = n_ctr * (size_t)(S.bounces + 2) * (size_t)std::max(1, S.path_samples);
-			size_t cap = std::min<size_t>(want, (free_b / 3) / 76);
-			cap = std::min<size_t>(cap, 0x7ffffff0u);
-			if(const char *e = std::getenv("YAFARAY_AMD_DFR_CAP"); e && atoi(e) > 0) cap = std::min<size_t>(cap, (size_t)atoi(e));   // tests: the overflow
-			bool ok_mem = cap > 0 && ensure(log_, d.dfr_kind, cap * 4) && ensure(log_, d.dfr_pp, cap * 16) && ensure(log_, d.dfr_wo, cap * 16) &&
-			              ensure(log_, d.dfr_a, cap * 16) && ensure(log_, d.dfr_emit, cap * 16) && ensure(log_, d.dfr_pix, cap * 8) &&
-			              ensure(log_, d.dfr_last, n_ctr * 4) &&
-			              ensure(log_, d.dfr_segoff, (size_t)S.n_seg * 4) && ensure(log_, d.dfr_misc, 16) && ensure(log_, d.dfr_its, 4096 * 4) &&
-			              ensure(log_, d.dfr_pcol, n_ctr * 16) && ensure(log_, d.dfr_idx, (size_t)S.n_seg * S.cap_a * 4) &&
-			              ensure(log_, d.dfr_nrec, (size_t)S.n_seg * 4);
-			if(ok_mem)
-			{
-				HIPCHECK(hipMemsetAsync(d.lpc.p, 0, n_ctr * 4, d.stream));
-				HIPCHECK(hipMemsetAsync(d.dfr_last.p, 0xff, n_ctr * 4, d.stream));
-				HIPCHECK(hipMemsetAsync(d.dfr_misc.p, 0, 16, d.stream));
-				HIPCHECK(hipMemsetAsync(d.dfr_its.p, 0, 4, d.stream));
-				HIPCHECK(hipMemsetAsync(d.dfr_pcol.p, 0, n_ctr * 16, d.stream));
-				S.lpc = (uint32_t *)d.lpc.p;
-				S.dfr_kind = (uint32_t *)d.dfr_kind.p;
-				S.dfr_pp = (float4 *)d.dfr_pp.p;
-				S.dfr_wo = (float4 *)d.dfr_wo.p;
-				S.dfr_a = (float4 *)d.dfr_a.p;
-				S.dfr_emit = (float4 *)d.dfr_emit.p;
-				S.dfr_pix = (uint2 *)d.dfr_pix.p;
-				S.dfr_last = (uint32_t *)d.dfr_last.p;
-				S.dfr_seg_off = (const uint32_t *)d.dfr_segoff.p;
-				S.dfr_cap = (uint32_t)cap;
-				S.lpc_mode = 3;
-				const bool ok = runSamples(n_total);
-				S.lpc_mode = 0;
-				if(!ok) return false;
-				uint32_t misc[2] = {0u, 0u};
-				std::vector<uint32_t> its(4096, 0u);
-				HIPCHECK(hipMemcpyAsync(misc, d.dfr_misc.p, 8, hipMemcpyDeviceToHost, d.stream));
-				HIPCHECK(hipMemcpyAsync(its.data(), d.dfr_its.p, its.size() * 4, hipMemcpyDeviceToHost, d.stream));
-				HIPCHECK(hipStreamSynchronize(d.stream));
-				if(its[0] > 4095u) misc[1] = 1u;   // more iterations than recorded starts: the count run serves
-				if(!misc[1])
-				{
-					bool cut = done < n_total;
-					if(!lpcBases(rp, pass_spp, jy0, jy1, group_render, cut)) return false;
-					if(cut)
-					{
-						done = 0;   // canceled before the pass rendered anything
-						return true;
-					}
-					const uint32_t total_slots = misc[0];
-					const uint32_t batch = S.n_seg * S.cap_a;
-					for(uint32_t r0 = 0; r0 < total_slots; r0 += batch)
-					{
-						PROF(KK_DFR, yafamd_dfr_nee(&S, &d.P[0], &d.Q[0], &cnt[0], r0, total_slots, (uint32_t *)d.dfr_idx.p, (uint32_t *)d.dfr_nrec.p,
-						                            d.stream));
-						DevQueues qs = d.Q[0];
-						qs.ray_tt = nullptr;
-						qs.perm = nullptr;
-						qs.tmin_dflt = S.ray_min_dist;
-						PROF(KK_TRACE, yafamd_launch_trace(&S, &qs, &cnt[0], &d.P[0], run_stats, d.lds_stack, (int *)d.spill.p, d.trace_grid, d.stream));
-						// every sample's terms of this batch, iteration range by iteration range (one record per sample and
-						// iteration; the ranges increase with the slots, so the additions keep the one-pass order)
-						const uint32_t r1 = std::min<uint64_t>((uint64_t)r0 + batch, total_slots);
-						for(uint32_t k = 0; k < its[0]; ++k)
-						{
-							const uint32_t a = std::max(its[1 + k], r0), b = std::min((k + 1 < its[0]) ? its[2 + k] : total_slots, r1);
-							if(b > a) PROF(KK_DFR, yafamd_dfr_accum(&S, &d.P[0], a, b, r0, (float4 *)d.dfr_pcol.p, d.stream));
-						}
-					}
-					PROF(KK_DFR, yafamd_dfr_fold(&S, (float4 *)d.samples.p, (uint32_t)n_ctr, (const float4 *)d.dfr_pcol.p, d.stream));
-					return true;
-				}
-				log_.info("Integrator: the deferred light pick's records exceed their budget (" + std::to_string(cap) +
-				          " slots); the pass renders again with a count run");
-			}
-		}
-		HIPCHECK(hipMemsetAsync(d.lpc.p, 0, n_ctr * 4, d.stream));
-		HIPCHECK(hipMemsetAsync(d.lpc_stats.p, 0, sizeof(DevStats) * (size_t)d.trace_grid, d.stream));
-		S.lpc = (uint32_t *)d.lpc.p;
-		S.lpc_mode = 1;
-		S.stats = (DevStats *)d.lpc_stats.p;
-		run_stats = S.stats;
-		auto on_chunk = rp.on_chunk;
-		rp.on_chunk = nullptr;   // progress is reported by the render proper
-		const bool ok = runSamples(n_total);
-		rp.on_chunk = on_chunk;
-		S.stats = dstats;
-		run_stats = dstats;
-		S.lpc_mode = 0;
-		if(!ok) return false;
-		bool cut = done < n_total;
-		if(!lpcBases(rp, pass_spp, jy0, jy1, group_render, cut)) return false;
-		if(cut)
-		{
-			done = 0;   // canceled before the pass rendered anything
-			return true;
-		}
-		S.lpc_mode = 2;
-		const bool ok2 = runSamples(n_total);
-		S.lpc_mode = 0;
-		return ok2;
-	};
+	for(size_t k = levels.size(); k-- > 0;)
+		PROF(KK_COMBINE, yafamd_launch_combine(&S, S.node_base + levels[k].first, S.node_base + levels[k].second, 0, nullptr, nullptr, 0, 0, d.stream));
+	PROF(KK_COMBINE, yafamd_launch_combine(&S, 0, (uint32_t)n, 1, (float4 *)d.samples.p, (const DevJob *)d.jobs.p, n_jobs, base, d.stream));
+	S.cur_level = 0;
+	return true;
+}
 
-	// The layers' first-hit pass over the `n_done` samples a pass rendered, chunk by chunk in the pass's own
-	// enumeration (the camera rays are regenerated: sampleAt / cameraRay with the pass's S), and the layer film
-	// beside every k_film launch (before it: k_film writes the weights both read)
-	auto runLayerHits = [&](uint64_t n_done) -> bool {
-		if(n_lay == 0) return true;
-		for(uint64_t base = 0; base < n_done; base += M)
+// one pass's samples; with the one-thread light pick a count run first (the paths only: closest
+// rays and shading, no estimates), then the counters' bases (lpcBases), then the render proper
+bool GpuRenderer::Run::runPass(uint64_t n_total, int pass_spp)
+{
+	if(!sch.lpc_on) return runSamples(n_total);
+	const size_t n_ctr = (size_t)W * H * (size_t)pass_spp;
+	const int budget = lpcBudget(n_ctr);
+	if(budget == LPC_FAILED) return false;
+	if(budget == LPC_HASH) return runSamples(n_total);
+	const int pick = runDeferredPick(n_total, pass_spp, n_ctr);
+	if(pick == DFR_FAILED) return false;
+	if(pick == DFR_KEPT) return true;
+	return runCountThenRender(n_total, pass_spp, n_ctr);
+}
+
+// one 4-B counter per camera sample of the pass (8.5 GB at 1080p x 1024 spp): above a budget of a
+// quarter of the device's free memory, or when the allocation fails, the pass falls back to the
+// hashed pick (matched statistically) instead of failing the render
+int GpuRenderer::Run::lpcBudget(size_t n_ctr)
+{
+	size_t free_b = 0, total_b = 0;
+	const bool have = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+	bool fits = d.lpc.bytes >= n_ctr * 4 || (have && n_ctr * 4 <= (free_b + d.lpc.bytes) / 4);
+	if(const char *e = std::getenv("YAFARAY_AMD_LPC_MAX_MB"); e && *e) fits = fits && (n_ctr * 4 >> 20) < (size_t)std::max(0, atoi(e));
+	auto tryEnsure = [](Buf &b, size_t bytes) {
+		if(b.p && b.bytes >= bytes) return true;
+		b.release();
+		if(hipMalloc(&b.p, std::max<size_t>(bytes, 16)) != hipSuccess)
 		{
-			const int n = (int)std::min<uint64_t>(M, n_done - base);
-			PROF(KK_LAYER_HITS, yafamd_launch_layer_hits(&S, &LY, (const DevJob *)d.jobs.p, n_jobs, base, n, d.stack_depth, d.stream));
+			b.p = nullptr;
+			(void)hipGetLastError();
+			return false;
 		}
-		layer_rays += n_done;
+		b.bytes = std::max<size_t>(bytes, 16);
 		return true;
 	};
-	auto layerFilm = [&](const DevFilm &F, const uint8_t *flags, void *out, int y0, int y1, int accumulate) -> bool {
-		if(n_lay == 0) return true;
-		PROF(KK_LAYER_FILM, yafamd_launch_layer_film(&F, &LY, (const float4 *)d.prim_ng.p, flags, (float4 *)d.lay_accum.p, (float4 *)out,
-		                                             (const float *)d.weights.p, y0, y1, S.clamp_samples, accumulate, d.stream));
-		return true;
-	};
+	bool can = fits && tryEnsure(d.lpc, n_ctr * 4) && tryEnsure(d.lpc_stats, sizeof(DevStats) * (size_t)d.trace_grid);
+	if(group_render)
+	{
+		// every member takes the same pick (the count run's bases are exchanged): fall back together
+		const int st = r.groupStatus(can ? 0 : 1);
+		if(st >= 2)
+		{
+			log_.error("GPU group: a member failed; render abandoned");
+			return LPC_FAILED;
+		}
+		can = st == 0;
+	}
+	if(!can)
+	{
+		log_.warning("Integrator: the one-thread light-pick counters (" + std::to_string(n_ctr * 4 >> 20) +
+		             " MB) exceed the memory budget; this pass picks lights by sample hash");
+		return LPC_HASH;
+	}
+	return LPC_COUNTERS;
+}
 
-	// ---- pass 0 (every pixel), then the adaptive passes (TiledIntegrator::render, integrator_tiled.cc:172-231) ----
-	const int passes = std::max(1, rp.aa.passes);
+// the deferred pick (r06): the pass once with every addition to a path colour kept as a record, the
+// lights picked from the counters' bases afterwards, the records folded in order — no count run.  A
+// group render (collective bases) and scenes it does not serve keep the count run; so does a pass whose
+// records overflow their budget (a third of the free memory), rendered again by runCountThenRender
+int GpuRenderer::Run::runDeferredPick(uint64_t n_total, int pass_spp, size_t n_ctr)
+{
+	if(group_render || !yafamd_dfr_eligible(&S)) return DFR_COUNT_RUN;
+	size_t free_b = 0, total_b = 0;
+	(void)hipMemGetInfo(&free_b, &total_b);
+	const size_t want = n_ctr * (size_t)(S.bounces + 2) * (size_t)std::max(1, S.path_samples);
+	size_t cap = std::min<size_t>(want, (free_b / 3) / 76);
+	cap = std::min<size_t>(cap, 0x7ffffff0u);
+	if(const char *e = std::getenv("YAFARAY_AMD_DFR_CAP"); e && atoi(e) > 0) cap = std::min<size_t>(cap, (size_t)atoi(e));   // tests: the overflow
+	bool ok_mem = cap > 0 && ensure(log_, d.dfr_kind, cap * 4) && ensure(log_, d.dfr_pp, cap * 16) && ensure(log_, d.dfr_wo, cap * 16) &&
+	              ensure(log_, d.dfr_a, cap * 16) && ensure(log_, d.dfr_emit, cap * 16) && ensure(log_, d.dfr_pix, cap * 8) &&
+	              ensure(log_, d.dfr_last, n_ctr * 4) &&
+	              ensure(log_, d.dfr_segoff, (size_t)S.n_seg * 4) && ensure(log_, d.dfr_misc, 16) && ensure(log_, d.dfr_its, 4096 * 4) &&
+	              ensure(log_, d.dfr_pcol, n_ctr * 16) && ensure(log_, d.dfr_idx, (size_t)S.n_seg * S.cap_a * 4) &&
+	              ensure(log_, d.dfr_nrec, (size_t)S.n_seg * 4);
+	if(!ok_mem) return DFR_COUNT_RUN;
+	HIPCHECK(hipMemsetAsync(d.lpc.p, 0, n_ctr * 4, d.stream));
+	HIPCHECK(hipMemsetAsync(d.dfr_last.p, 0xff, n_ctr * 4, d.stream));
+	HIPCHECK(hipMemsetAsync(d.dfr_misc.p, 0, 16, d.stream));
+	HIPCHECK(hipMemsetAsync(d.dfr_its.p, 0, 4, d.stream));
+	HIPCHECK(hipMemsetAsync(d.dfr_pcol.p, 0, n_ctr * 16, d.stream));
+	S.lpc = (uint32_t *)d.lpc.p;
+	S.dfr_kind = (uint32_t *)d.dfr_kind.p;
+	S.dfr_pp = (float4 *)d.dfr_pp.p;
+	S.dfr_wo = (float4 *)d.dfr_wo.p;
+	S.dfr_a = (float4 *)d.dfr_a.p;
+	S.dfr_emit = (float4 *)d.dfr_emit.p;
+	S.dfr_pix = (uint2 *)d.dfr_pix.p;
+	S.dfr_last = (uint32_t *)d.dfr_last.p;
+	S.dfr_seg_off = (const uint32_t *)d.dfr_segoff.p;
+	S.dfr_cap = (uint32_t)cap;
+	S.lpc_mode = 3;
+	const bool ok = runSamples(n_total);
+	S.lpc_mode = 0;
+	if(!ok) return DFR_FAILED;
+	uint32_t misc[2] = {0u, 0u};
+	std::vector<uint32_t> its(4096, 0u);
+	HIPCHECK(hipMemcpyAsync(misc, d.dfr_misc.p, 8, hipMemcpyDeviceToHost, d.stream));
+	HIPCHECK(hipMemcpyAsync(its.data(), d.dfr_its.p, its.size() * 4, hipMemcpyDeviceToHost, d.stream));
+	HIPCHECK(hipStreamSynchronize(d.stream));
+	if(its[0] > 4095u) misc[1] = 1u;   // more iterations than recorded starts: the count run serves
+	if(misc[1])
+	{
+		log_.info("Integrator: the deferred light pick's records exceed their budget (" + std::to_string(cap) +
+		          " slots); the pass renders again with a count run");
+		return DFR_COUNT_RUN;
+	}
+	bool cut = done < n_total;
+	if(!r.lpcBases(rp, pass_spp, jy0, jy1, group_render, cut)) return DFR_FAILED;
+	if(cut)
+	{
+		done = 0;   // canceled before the pass rendered anything
+		return DFR_KEPT;
+	}
+	const uint32_t total_slots = misc[0];
+	const uint32_t batch = S.n_seg * S.cap_a;
+	for(uint32_t r0 = 0; r0 < total_slots; r0 += batch)
+	{
+		PROF(KK_DFR, yafamd_dfr_nee(&S, &d.P[0], &d.Q[0], &cnt[0], r0, total_slots, (uint32_t *)d.dfr_idx.p, (uint32_t *)d.dfr_nrec.p,
+		                            d.stream));
+		DevQueues qs = d.Q[0];
+		qs.ray_tt = nullptr;
+		qs.perm = nullptr;
+		qs.tmin_dflt = S.ray_min_dist;
+		PROF(KK_TRACE, yafamd_launch_trace(&S, &qs, &cnt[0], &d.P[0], run_stats, d.lds_stack, (int *)d.spill.p, d.trace_grid, d.stream));
+		// every sample's terms of this batch, iteration range by iteration range (one record per sample and
+		// iteration; the ranges increase with the slots, so the additions keep the one-pass order)
+		const uint32_t r1 = std::min<uint64_t>((uint64_t)r0 + batch, total_slots);
+		for(uint32_t k = 0; k < its[0]; ++k)
+		{
+			const uint32_t a = std::max(its[1 + k], r0), b = std::min((k + 1 < its[0]) ? its[2 + k] : total_slots, r1);
+			if(b > a) PROF(KK_DFR, yafamd_dfr_accum(&S, &d.P[0], a, b, r0, (float4 *)d.dfr_pcol.p, d.stream));
+		}
+	}
+	PROF(KK_DFR, yafamd_dfr_fold(&S, (float4 *)d.samples.p, (uint32_t)n_ctr, (const float4 *)d.dfr_pcol.p, d.stream));
+	return DFR_KEPT;
+}
+
+// the count run (paths only, counting into its own statistics, no progress callbacks), the counters' bases, then
+// the render proper picking from them
+bool GpuRenderer::Run::runCountThenRender(uint64_t n_total, int pass_spp, size_t n_ctr)
+{
+	HIPCHECK(hipMemsetAsync(d.lpc.p, 0, n_ctr * 4, d.stream));
+	HIPCHECK(hipMemsetAsync(d.lpc_stats.p, 0, sizeof(DevStats) * (size_t)d.trace_grid, d.stream));
+	S.lpc = (uint32_t *)d.lpc.p;
+	S.lpc_mode = 1;
+	S.stats = (DevStats *)d.lpc_stats.p;
+	run_stats = S.stats;
+	auto on_chunk = rp.on_chunk;
+	rp.on_chunk = nullptr;   // progress is reported by the render proper
+	const bool ok = runSamples(n_total);
+	rp.on_chunk = on_chunk;
+	S.stats = dstats;
+	run_stats = dstats;
+	S.lpc_mode = 0;
+	if(!ok) return false;
+	bool cut = done < n_total;
+	if(!r.lpcBases(rp, pass_spp, jy0, jy1, group_render, cut)) return false;
+	if(cut)
+	{
+		done = 0;   // canceled before the pass rendered anything
+		return true;
+	}
+	S.lpc_mode = 2;
+	const bool ok2 = runSamples(n_total);
+	S.lpc_mode = 0;
+	return ok2;
+}
+
+// The layers' first-hit pass over the `n_done` samples a pass rendered, chunk by chunk in the pass's own
+// enumeration (the camera rays are regenerated: sampleAt / cameraRay with the pass's S)
+bool GpuRenderer::Run::runLayerHits(uint64_t n_done)
+{
+	if(n_lay == 0) return true;
+	for(uint64_t base = 0; base < n_done; base += M)
+	{
+		const int n = (int)std::min<uint64_t>(M, n_done - base);
+		PROF(KK_LAYER_HITS, yafamd_launch_layer_hits(&S, &LY, (const DevJob *)d.jobs.p, n_jobs, base, n, d.stack_depth, d.stream));
+	}
+	layer_rays += n_done;
+	return true;
+}
+
+// the layer film beside every k_film launch (before it: k_film writes the weights both read)
+bool GpuRenderer::Run::layerFilm(const DevFilm &F, const uint8_t *flags, void *out, int y0, int y1, int accumulate)
+{
+	if(n_lay == 0) return true;
+	PROF(KK_LAYER_FILM, yafamd_launch_layer_film(&F, &LY, (const float4 *)d.prim_ng.p, flags, (float4 *)d.lay_accum.p, (float4 *)out,
+	                                             (const float *)d.weights.p, y0, y1, S.clamp_samples, accumulate, d.stream));
+	return true;
+}
+
+// the film of the owned rows (and its layers) from the pass's samples
+bool GpuRenderer::Run::filmRows(const DevFilm &F, const uint8_t *flags, int accumulate)
+{
+	for(const auto &rows : owned_rows_)
+	{
+		if(!layerFilm(F, flags, d.lay_film.p, rows.first, rows.second, accumulate)) return false;
+		PROF(KK_FILM, yafamd_launch_film(&F, (const float4 *)d.samples.p, flags, (float4 *)d.accum.p, (float4 *)d.film.p, (float *)d.weights.p,
+		                                 rows.first, rows.second, S.clamp_samples, accumulate, d.stream));
+	}
+	return true;
+}
+
+// ---- pass 0 (every pixel), then the adaptive passes (TiledIntegrator::render, integrator_tiled.cc:172-231) ----
+bool GpuRenderer::Run::setupFilm()
+{
 	S.aa_multipass = passes > 1 ? 1 : 0;
 	S.pass_offset = 0;
 	S.plist = nullptr;
@@ -2880,35 +3106,38 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 		if(!allocCopy(log_, d.tile_rank, rp.tile_rank.data(), rp.tile_rank.size())) return false;
 		rp.film.tile_rank = (const uint32_t *)d.tile_rank.p;
 	}
-	// per-tile callbacks: the partial film of a pass (before its film launch adds to the accumulators)
-	const bool tiles_cb = (bool)rp.on_tiles && rp.shard_world == 1 && groupWorld() <= 1;
-	auto emitTiles = [&](int pass, const uint8_t *flags, int accumulate) -> bool {
-		if(!tiles_cb) return true;
-		if(!ensure(log_, d.pfilm, (size_t)W * H * sizeof(float4))) return false;
-		DevFilm Fp = rp.film;
-		Fp.partial = 1;
-		PROF(KK_FILM, yafamd_launch_film(&Fp, (const float4 *)d.samples.p, flags, (float4 *)d.accum.p, (float4 *)d.pfilm.p, (float *)d.weights.p, 0, H,
-		                            S.clamp_samples, accumulate, d.stream));
-		if(!layerFilm(Fp, flags, d.lay_pfilm.p, 0, H, accumulate)) return false;
-		std::vector<float> host((size_t)W * H * 4), host_layers((size_t)n_lay * W * H * 4);
-		HIPCHECK(hipMemcpyAsync(host.data(), d.pfilm.p, host.size() * sizeof(float), hipMemcpyDeviceToHost, d.stream));
-		if(n_lay > 0) HIPCHECK(hipMemcpyAsync(host_layers.data(), d.lay_pfilm.p, host_layers.size() * sizeof(float), hipMemcpyDeviceToHost, d.stream));
-		HIPCHECK(hipStreamSynchronize(d.stream));
-		rp.on_tiles(pass, host, host_layers);
-		return true;
-	};
-	uint64_t samples_total = total;
+	return true;
+}
+
+// per-tile callbacks: the partial film of a pass (before its film launch adds to the accumulators)
+bool GpuRenderer::Run::emitTiles(int pass, const uint8_t *flags, int accumulate)
+{
+	const bool tiles_cb = (bool)rp.on_tiles && rp.shard_world == 1 && r.groupWorld() <= 1;
+	if(!tiles_cb) return true;
+	if(!ensure(log_, d.pfilm, (size_t)W * H * sizeof(float4))) return false;
+	DevFilm Fp = rp.film;
+	Fp.partial = 1;
+	PROF(KK_FILM, yafamd_launch_film(&Fp, (const float4 *)d.samples.p, flags, (float4 *)d.accum.p, (float4 *)d.pfilm.p, (float *)d.weights.p, 0, H,
+	                            S.clamp_samples, accumulate, d.stream));
+	if(!layerFilm(Fp, flags, d.lay_pfilm.p, 0, H, accumulate)) return false;
+	std::vector<float> host((size_t)W * H * 4), host_layers((size_t)n_lay * W * H * 4);
+	HIPCHECK(hipMemcpyAsync(host.data(), d.pfilm.p, host.size() * sizeof(float), hipMemcpyDeviceToHost, d.stream));
+	if(n_lay > 0) HIPCHECK(hipMemcpyAsync(host_layers.data(), d.lay_pfilm.p, host_layers.size() * sizeof(float), hipMemcpyDeviceToHost, d.stream));
+	HIPCHECK(hipStreamSynchronize(d.stream));
+	rp.on_tiles(pass, host, host_layers);
+	return true;
+}
+
+// pass 0: every pixel's samples and their film — or, resuming, only the loaded film normalised
+bool GpuRenderer::Run::firstPass()
+{
+	samples_total = total;
 	if(rp.resumed)
 	{
 		// renderPass(0, sampling_offset): no samples; the loaded film is only normalised
 		DevFilm F0 = rp.film;
 		F0.spp = 0;
-		for(const auto &r : owned_rows_)
-		{
-			if(!layerFilm(F0, nullptr, d.lay_film.p, r.first, r.second, 1)) return false;
-			PROF(KK_FILM, yafamd_launch_film(&F0, (const float4 *)d.samples.p, nullptr, (float4 *)d.accum.p, (float4 *)d.film.p,
-			                            (float *)d.weights.p, r.first, r.second, S.clamp_samples, 1, d.stream));
-		}
+		if(!filmRows(F0, nullptr, 1)) return false;
 		samples_total = 0;
 		sampling_offset_ = rp.resume_sampling_offset;
 	}
@@ -2928,206 +3157,198 @@ bool GpuRenderer::render(RenderParams &rp, volatile bool *canceled)
 			samples_total = done / (uint64_t)spp * (uint64_t)spp;
 		}
 		if(done == total && !emitTiles(0, nullptr, 0)) return false;
-		for(const auto &r : owned_rows_)
-		{
-			if(!layerFilm(rp.film, done_flags, d.lay_film.p, r.first, r.second, 0)) return false;
-			PROF(KK_FILM, yafamd_launch_film(&rp.film, (const float4 *)d.samples.p, done_flags, (float4 *)d.accum.p, (float4 *)d.film.p,
-			                            (float *)d.weights.p, r.first, r.second, S.clamp_samples, 0, d.stream));
-		}
+		if(!filmRows(rp.film, done_flags, 0)) return false;
 		// renderPass sets the sampling offset before its workers start (integrator_tiled.cc:244), so a
 		// canceled pass advances it too
 		sampling_offset_ = (uint32_t)spp;
 	}
 	passes_done_ = 1;
-	if(passes > 1)
+	return true;
+}
+
+// diagnostics (YAFARAY_AMD_AA_DUMP=prefix): the pass's flags as W*H bytes
+bool GpuRenderer::Run::dumpAaFlags(int pass)
+{
+	if(const char *dump = getenv("YAFARAY_AMD_AA_DUMP"); dump && *dump)
 	{
-		if(!ensure(log_, d.aa_flags, (size_t)W * H) || !ensure(log_, d.aa_plist, (size_t)W * H * 4)) return false;
-		float threshold = rp.aa.threshold, sample_multiplier = 1.f, light_multiplier = 1.f, indirect_multiplier = 1.f;
-		bool threshold_changed = true;
-		int acum = spp, resampled = 0;
-		int resampled_local = 0;   // of them in this member's rows (+ halo rows): the pixels it renders
-		const int floor_pixels = (int)floorf(rp.aa.resampled_floor * (float)(W * H) / 100.f);
-		for(int pass = 1; pass < passes; ++pass)
+		std::vector<uint8_t> hf((size_t)W * H);
+		HIPCHECK(hipMemcpy(hf.data(), d.aa_flags.p, hf.size(), hipMemcpyDeviceToHost));
+		if(FILE *f = fopen((std::string(dump) + "_pass" + std::to_string(pass) + ".bin").c_str(), "wb"))
 		{
-			if(group_render && fault_pass_ == pass)
-			{
-				log_.error("GPU group: injected failure of member " + std::to_string(rp.shard_rank) + " at pass " + std::to_string(pass + 1));
-				return false;
-			}
-			if(group_render)
-			{
-				// every member's film of the last pass is complete: agree on going on (a member that was
-				// canceled or failed stops everyone here), then every member assembles the whole accumulated
-				// film — nextPass compares pixels with their neighbours across band boundaries
-				HIPCHECK(hipStreamSynchronize(d.stream));
-				const int st = groupStatus((canceled && *canceled) ? 1 : 0);
-				if(st >= 2)
-				{
-					log_.error("GPU group: a member failed; render abandoned");
-					return false;
-				}
-				if(st == 1) break;
-				if(!exchangeRows(rp.band_bounds, XR_ACCUM, true)) return false;
-			}
-			else if(canceled && *canceled) break;
-			sample_multiplier *= rp.aa.sample_multiplier_factor;
-			light_multiplier *= rp.aa.light_sample_multiplier_factor;
-			indirect_multiplier *= rp.aa.indirect_sample_multiplier_factor;
-			S.fg_pass_samples = (int)ceilf((float)std::max(1, S.fg_samples) * indirect_multiplier);
-			if(light_mult)
-			{
-				HIPCHECK(hipStreamSynchronize(d.stream));   // the previous pass's staging copy is consumed
-				lightLayout(light_multiplier, d.pass_lights);
-				HIPCHECK(hipMemcpyAsync(d.lights.p, d.pass_lights.data(), d.pass_lights.size() * sizeof(DevLight), hipMemcpyHostToDevice,
-				                        d.stream));
-			}
-			const bool skip = resampled <= 0.f && !threshold_changed;
-			if(rp.on_next_pass)
-			{
-				HIPCHECK(hipStreamSynchronize(d.stream));
-				rp.on_next_pass(skip);
-			}
-			if(skip) {}   // nextPass(..., skipNextPass = true)
-			else
-			{
-				// the flags of the whole film; the pixel list restricted to the rows whose samples this
-				// member's film rows gather (its band + halo rows)
-				uint32_t count = 0, local = 0;
-				int ry0 = 0, ry1 = H;
-				if(group_render)
-				{
-					ry0 = std::max(0, rp.shard_y0 - rp.film.reach_fwd);
-					ry1 = std::min(H, rp.shard_y1 + rp.film.reach_back);
-				}
-				PROF(KK_AA, yafamd_aa_next_pass((const float4 *)d.accum.p, (const float *)d.weights.p, W, H, ts, &rp.aa.dev, threshold,
-				                             (uint8_t *)d.aa_flags.p, (uint32_t *)d.aa_plist.p, &count, ry0, ry1, &local, d.stream));
-				resampled = (int)count;
-				resampled_local = (int)local;
-				threshold_changed = false;
-				if(const char *dump = getenv("YAFARAY_AMD_AA_DUMP"); dump && *dump)
-				{
-					// diagnostics: the pass's flags as W*H bytes
-					std::vector<uint8_t> hf((size_t)W * H);
-					HIPCHECK(hipMemcpy(hf.data(), d.aa_flags.p, hf.size(), hipMemcpyDeviceToHost));
-					if(FILE *f = fopen((std::string(dump) + "_pass" + std::to_string(pass) + ".bin").c_str(), "wb"))
-					{
-						fwrite(hf.data(), 1, hf.size(), f);
-						fclose(f);
-					}
-				}
-			}
-			const int n_pass = (int)ceilf(rp.aa.inc_samples * sample_multiplier);
-			{
-				std::ostringstream os;
-				os << "Rendering pass " << pass + 1 << " of " << passes << ", resampling " << resampled << " pixels x " << n_pass << " samples.";
-				log_.info(os.str());
-			}
-			if(resampled > 0 && n_pass > 0)
-			{
-				if(!ensure(log_, d.samples, (size_t)W * H * n_pass * sizeof(float4))) return false;
-				S.spp = n_pass;
-				S.pass_offset = (uint32_t)acum;
-				S.plist = (const uint32_t *)d.aa_plist.p;
-				rp.film.spp = n_pass;
-				rp.film.sample_offset = S.base_offset + (uint32_t)acum;
-				const uint64_t n_total = (uint64_t)resampled_local * (uint64_t)n_pass;
-				if(!runPass(n_total, n_pass)) return false;
-				if(n_lay > 0)
-				{
-					// the pass's records (and albedo plane) in the pass's sample indexing
-					const size_t per_sample = (size_t)W * H * n_pass * sizeof(float4);
-					if(!ensureLayerBufs({{&d.lay_rec, per_sample}, {&d.lay_albedo, LY.albedo ? per_sample : 0}})) return false;
-					LY.rec = (float4 *)d.lay_rec.p;
-					if(LY.albedo) LY.albedo = (float4 *)d.lay_albedo.p;
-					if(!runLayerHits(done)) return false;
-				}
-				if(done < n_total)
-					HIPCHECK(yafamd_launch_done_flags(&S, (const DevJob *)d.jobs.p, n_jobs, (uint32_t)resampled_local, (uint32_t)(done / (uint64_t)n_pass),
-					                                  (uint8_t *)d.aa_flags.p, d.stream));
-				if(done == n_total && !emitTiles(passes_done_, (const uint8_t *)d.aa_flags.p, 1)) return false;
-				for(const auto &r : owned_rows_)
-				{
-					if(!layerFilm(rp.film, (const uint8_t *)d.aa_flags.p, d.lay_film.p, r.first, r.second, 1)) return false;
-					PROF(KK_FILM, yafamd_launch_film(&rp.film, (const float4 *)d.samples.p, (const uint8_t *)d.aa_flags.p, (float4 *)d.accum.p,
-					                            (float4 *)d.film.p, (float *)d.weights.p, r.first, r.second, S.clamp_samples, 1, d.stream));
-				}
-				samples_total += done / (uint64_t)n_pass * (uint64_t)n_pass;
-				sampling_offset_ = (uint32_t)(acum + n_pass);   // renderPass: setSamplingOffset(offset + samples), :244
-				if(done < n_total)
-				{
-					// canceled mid-pass; a group member stops at the next status agreement, with the others
-					if(group_render)
-					{
-						acum += n_pass;
-						continue;
-					}
-					break;
-				}
-				++passes_done_;
-			}
-			acum += n_pass;
-			if(resampled < floor_pixels)
-			{
-				const float ratio = std::min(8.f, ((float)floor_pixels / resampled));
-				threshold *= (1.f - 0.1f * ratio);
-				if(threshold > 0.f) threshold_changed = true;
-			}
-		}
-		S.spp = spp;
-		S.pass_offset = 0;
-		S.plist = nullptr;
-		S.fg_pass_samples = 0;
-		rp.film.spp = spp;
-		if(light_mult)
-		{
-			HIPCHECK(hipStreamSynchronize(d.stream));
-			lightLayout(1.f, d.pass_lights);
-			HIPCHECK(hipMemcpy(d.lights.p, d.pass_lights.data(), d.pass_lights.size() * sizeof(DevLight), hipMemcpyHostToDevice));
+			fwrite(hf.data(), 1, hf.size(), f);
+			fclose(f);
 		}
 	}
+	return true;
+}
+
+// the adaptive passes: nextPass flags the pixels above the threshold, the pass renders them again
+bool GpuRenderer::Run::adaptivePasses()
+{
+	if(passes <= 1) return true;
+	if(!ensure(log_, d.aa_flags, (size_t)W * H) || !ensure(log_, d.aa_plist, (size_t)W * H * 4)) return false;
+	AaState aa;
+	aa.threshold = rp.aa.threshold;
+	aa.acum = spp;
+	const int floor_pixels = (int)floorf(rp.aa.resampled_floor * (float)(W * H) / 100.f);
+	for(int pass = 1; pass < passes; ++pass)
+	{
+		if(group_render && r.fault_pass_ == pass)
+		{
+			log_.error("GPU group: injected failure of member " + std::to_string(rp.shard_rank) + " at pass " + std::to_string(pass + 1));
+			return false;
+		}
+		if(group_render)
+		{
+			// every member's film of the last pass is complete: agree on going on (a member that was
+			// canceled or failed stops everyone here), then every member assembles the whole accumulated
+			// film — nextPass compares pixels with their neighbours across band boundaries
+			HIPCHECK(hipStreamSynchronize(d.stream));
+			const int st = r.groupStatus((canceled && *canceled) ? 1 : 0);
+			if(st >= 2)
+			{
+				log_.error("GPU group: a member failed; render abandoned");
+				return false;
+			}
+			if(st == 1) break;
+			if(!r.exchangeRows(rp.band_bounds, XR_ACCUM, true)) return false;
+		}
+		else if(canceled && *canceled) break;
+		aa.sample_multiplier *= rp.aa.sample_multiplier_factor;
+		aa.light_multiplier *= rp.aa.light_sample_multiplier_factor;
+		aa.indirect_multiplier *= rp.aa.indirect_sample_multiplier_factor;
+		S.fg_pass_samples = (int)ceilf((float)std::max(1, S.fg_samples) * aa.indirect_multiplier);
+		if(light_mult)
+		{
+			HIPCHECK(hipStreamSynchronize(d.stream));   // the previous pass's staging copy is consumed
+			layoutLights(aa.light_multiplier, d.pass_lights);
+			HIPCHECK(hipMemcpyAsync(d.lights.p, d.pass_lights.data(), d.pass_lights.size() * sizeof(DevLight), hipMemcpyHostToDevice,
+			                        d.stream));
+		}
+		const bool skip = aa.resampled <= 0.f && !aa.threshold_changed;
+		if(rp.on_next_pass)
+		{
+			HIPCHECK(hipStreamSynchronize(d.stream));
+			rp.on_next_pass(skip);
+		}
+		if(skip) {}   // nextPass(..., skipNextPass = true)
+		else
+		{
+			// the flags of the whole film; the pixel list restricted to the rows whose samples this
+			// member's film rows gather (its band + halo rows)
+			uint32_t count = 0, local = 0;
+			int ry0 = 0, ry1 = H;
+			if(group_render)
+			{
+				ry0 = std::max(0, rp.shard_y0 - rp.film.reach_fwd);
+				ry1 = std::min(H, rp.shard_y1 + rp.film.reach_back);
+			}
+			PROF(KK_AA, yafamd_aa_next_pass((const float4 *)d.accum.p, (const float *)d.weights.p, W, H, ts, &rp.aa.dev, aa.threshold,
+			                             (uint8_t *)d.aa_flags.p, (uint32_t *)d.aa_plist.p, &count, ry0, ry1, &local, d.stream));
+			aa.resampled = (int)count;
+			aa.resampled_local = (int)local;
+			aa.threshold_changed = false;
+			if(!dumpAaFlags(pass)) return false;
+		}
+		const int n_pass = (int)ceilf(rp.aa.inc_samples * aa.sample_multiplier);
+		{
+			std::ostringstream os;
+			os << "Rendering pass " << pass + 1 << " of " << passes << ", resampling " << aa.resampled << " pixels x " << n_pass << " samples.";
+			log_.info(os.str());
+		}
+		if(aa.resampled > 0 && n_pass > 0)
+		{
+			if(!ensure(log_, d.samples, (size_t)W * H * n_pass * sizeof(float4))) return false;
+			S.spp = n_pass;
+			S.pass_offset = (uint32_t)aa.acum;
+			S.plist = (const uint32_t *)d.aa_plist.p;
+			rp.film.spp = n_pass;
+			rp.film.sample_offset = S.base_offset + (uint32_t)aa.acum;
+			const uint64_t n_total = (uint64_t)aa.resampled_local * (uint64_t)n_pass;
+			if(!runPass(n_total, n_pass)) return false;
+			if(n_lay > 0)
+			{
+				// the pass's records (and albedo plane) in the pass's sample indexing
+				const size_t per_sample = (size_t)W * H * n_pass * sizeof(float4);
+				if(!ensureLayerBufs({{&d.lay_rec, per_sample}, {&d.lay_albedo, LY.albedo ? per_sample : 0}})) return false;
+				LY.rec = (float4 *)d.lay_rec.p;
+				if(LY.albedo) LY.albedo = (float4 *)d.lay_albedo.p;
+				if(!runLayerHits(done)) return false;
+			}
+			if(done < n_total)
+				HIPCHECK(yafamd_launch_done_flags(&S, (const DevJob *)d.jobs.p, n_jobs, (uint32_t)aa.resampled_local, (uint32_t)(done / (uint64_t)n_pass),
+				                                  (uint8_t *)d.aa_flags.p, d.stream));
+			if(done == n_total && !emitTiles(passes_done_, (const uint8_t *)d.aa_flags.p, 1)) return false;
+			if(!filmRows(rp.film, (const uint8_t *)d.aa_flags.p, 1)) return false;
+			samples_total += done / (uint64_t)n_pass * (uint64_t)n_pass;
+			sampling_offset_ = (uint32_t)(aa.acum + n_pass);   // renderPass: setSamplingOffset(offset + samples), :244
+			if(done < n_total)
+			{
+				// canceled mid-pass; a group member stops at the next status agreement, with the others
+				if(group_render)
+				{
+					aa.acum += n_pass;
+					continue;
+				}
+				break;
+			}
+			++passes_done_;
+		}
+		aa.acum += n_pass;
+		if(aa.resampled < floor_pixels)
+		{
+			const float ratio = std::min(8.f, ((float)floor_pixels / aa.resampled));
+			aa.threshold *= (1.f - 0.1f * ratio);
+			if(aa.threshold > 0.f) aa.threshold_changed = true;
+		}
+	}
+	S.spp = spp;
+	S.pass_offset = 0;
+	S.plist = nullptr;
+	S.fg_pass_samples = 0;
+	rp.film.spp = spp;
+	if(light_mult)
+	{
+		HIPCHECK(hipStreamSynchronize(d.stream));
+		layoutLights(1.f, d.pass_lights);
+		HIPCHECK(hipMemcpy(d.lights.p, d.pass_lights.data(), d.pass_lights.size() * sizeof(DevLight), hipMemcpyHostToDevice));
+	}
+	return true;
+}
+
+// the stage guard (kernels.hip g_shade_stage_err): an entry in a stage its iteration does not imply
+bool GpuRenderer::Run::checkStageGuard()
+{
+	uint32_t err[32] = {};
+	const int n_err = yafamd_shade_stage_errors(err, 32);
+	if(n_err <= 0)
+	{
+		log_.error("Integrator: the stage guard of k_shade could not be read");
+		return false;
+	}
+	for(int k = 0; k < n_err && k < 32; ++k)
+		if(err[k])
+		{
+			log_.error("Integrator: k_shade iteration " + std::to_string(k) + (k == n_err - 1 ? " or later" : "") + " met " + std::to_string(err[k]) +
+			           " entries of another stage than its stage-specialised kernel handles (YAFARAY_AMD_SHADE_STAGES=0 renders without them)");
+			return false;
+		}
+	return true;
+}
+
+// the render's time, the stage guard, the statistics and the kernel times
+bool GpuRenderer::Run::finish()
+{
 	HIPCHECK(hipEventRecord(d.ev_pool[1], d.stream));
 	HIPCHECK(hipStreamSynchronize(d.stream));
 	float ms = 0.f;
 	HIPCHECK(hipEventElapsedTime(&ms, d.ev_pool[0], d.ev_pool[1]));
-	if(shade_staged)
-	{
-		// the stage guard (kernels.hip g_shade_stage_err): an entry in a stage its iteration does not imply
-		uint32_t err[32] = {};
-		const int n_err = yafamd_shade_stage_errors(err, 32);
-		if(n_err <= 0)
-		{
-			log_.error("Integrator: the stage guard of k_shade could not be read");
-			return false;
-		}
-		for(int k = 0; k < n_err && k < 32; ++k)
-			if(err[k])
-			{
-				log_.error("Integrator: k_shade iteration " + std::to_string(k) + (k == n_err - 1 ? " or later" : "") + " met " + std::to_string(err[k]) +
-				           " entries of another stage than its stage-specialised kernel handles (YAFARAY_AMD_SHADE_STAGES=0 renders without them)");
-				return false;
-			}
-	}
+	if(shade_staged && !checkStageGuard()) return false;
 	DevStats hs{};
 	{
 		std::vector<DevStats> per_block(2 * (size_t)d.trace_grid);   // both ranges (the early shadow parts' is the second)
 		HIPCHECK(hipMemcpy(per_block.data(), d.stats.p, sizeof(DevStats) * per_block.size(), hipMemcpyDeviceToHost));
-		for(const DevStats &b : per_block)
-		{
-			hs.closest_rays += b.closest_rays;
-			hs.shadow_rays += b.shadow_rays;
-			hs.node_visits += b.node_visits;
-			hs.tri_tests += b.tri_tests;
-			hs.shade_entries += b.shade_entries;
-			hs.nee_requests += b.nee_requests;
-			hs.gather_queries += b.gather_queries;
-			hs.gather_visits += b.gather_visits;
-			hs.gather_photons += b.gather_photons;
-			hs.gather_accepts += b.gather_accepts;
-			hs.gather_overflows += b.gather_overflows;
-			hs.fg_paths += b.fg_paths;
-			hs.fg_lookups += b.fg_lookups;
-			hs.fg_nearest_visits += b.fg_nearest_visits;
-		}
+		for(const DevStats &b : per_block) hs += b;   // (the render's kernels leave the pre-gather's two fields zero)
 		if(d.pre_stats_valid)
 		{
 			DevStats pre{};

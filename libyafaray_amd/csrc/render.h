@@ -291,6 +291,7 @@ class GpuRenderer
 		struct Impl;
 
 	private:
+		struct Run;   // the state and the stages of one render() call (render.cc)
 		void *d_comm() const;
 		bool groupCounts(uint32_t mine, std::vector<uint32_t> &all);
 		bool groupConcat(int kind, const std::vector<uint32_t> &counts);
