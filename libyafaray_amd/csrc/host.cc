@@ -2144,19 +2144,13 @@ bool Scene::render(const Callbacks &cb, yafaray_ProgressBarCallback_t progress, 
 		}
 		// film (imagefilm.cc:129-173)
 		DevFilm &F = rp.film;
-		float filterw = static_cast<float>(s.aa_pixelwidth * 0.5);
-		float (*ff)(float, float) = hm::filterBox;
-		if(s.filter == "mitchell") { ff = hm::filterMitchell; filterw *= 2.6f; }
-		else if(s.filter == "lanczos") ff = hm::filterLanczos;
-		else if(s.filter == "gauss") { ff = hm::filterGauss; filterw *= 2.f; }
-		filterw = std::min(std::max(0.501f, filterw), 0.5f * 8);
-		const float scale = 1.f / 16.f;
-		for(int y = 0; y < 16; ++y)
-			for(int x = 0; x < 16; ++x) F.table[y * 16 + x] = ff((x + .5f) * scale, (y + .5f) * scale);
-		F.filterw = filterw;
-		F.table_scale = static_cast<float>(0.9999 * 16 / filterw);
-		F.reach_fwd = std::max(0, (int)((double)filterw + (.5 - 1.4e-11)));
-		F.reach_back = std::max(0, -(int)(-(double)filterw + (.5 - 1.4e-11)));
+		const hm::FilmSetup fs = hm::filmSetup(s.filter == "mitchell" ? hm::FILM_MITCHELL : s.filter == "lanczos" ? hm::FILM_LANCZOS
+		                                       : s.filter == "gauss" ? hm::FILM_GAUSS : hm::FILM_BOX, s.aa_pixelwidth);
+		std::memcpy(F.table, fs.table, sizeof(F.table));
+		F.filterw = fs.filterw;
+		F.table_scale = fs.table_scale;
+		F.reach_fwd = fs.reach_fwd;
+		F.reach_back = fs.reach_back;
 		F.width = s.width;
 		F.height = s.height;
 		F.crop_x0 = s.xstart;

@@ -92,6 +92,36 @@ inline float filterLanczos(float dx, float dy)
 	return 0.f;
 }
 
+// The film's filter set-up (ImageFilm::ImageFilm, imagefilm.cc:129-162): the filter half-width, the 16 x 16
+// table of the filter function, the table scale, and the footprint reach that follows from them: a sample at
+// sub-pixel dx in [0, 1) splats onto offsets roundToInt(dx - filterw) .. roundToInt(dx + filterw - 1)
+// (imagefilm.cc:684-687), so a pixel's sources lie in [x - reach_fwd, x + reach_back].
+enum FilmFilter : int { FILM_BOX = 0, FILM_GAUSS = 1, FILM_MITCHELL = 2, FILM_LANCZOS = 3 };
+struct FilmSetup
+{
+	float table[256];
+	float filterw, table_scale;
+	int reach_fwd, reach_back;
+};
+inline FilmSetup filmSetup(int filter, float pixelwidth)
+{
+	FilmSetup F;
+	float filterw = static_cast<float>(pixelwidth * 0.5);
+	float (*ff)(float, float) = filterBox;
+	if(filter == FILM_MITCHELL) { ff = filterMitchell; filterw *= 2.6f; }
+	else if(filter == FILM_LANCZOS) ff = filterLanczos;
+	else if(filter == FILM_GAUSS) { ff = filterGauss; filterw *= 2.f; }
+	filterw = std::min(std::max(0.501f, filterw), 0.5f * 8);
+	const float scale = 1.f / 16.f;
+	for(int y = 0; y < 16; ++y)
+		for(int x = 0; x < 16; ++x) F.table[y * 16 + x] = ff((x + .5f) * scale, (y + .5f) * scale);
+	F.filterw = filterw;
+	F.table_scale = static_cast<float>(0.9999 * 16 / filterw);
+	F.reach_fwd = std::max(0, (int)((double)filterw + (.5 - 1.4e-11)));
+	F.reach_back = std::max(0, -(int)(-(double)filterw + (.5 - 1.4e-11)));
+	return F;
+}
+
 // include/color/color.h:338-343 (sRGB -> linear, FAST_MATH pow)
 inline float linearFromSrgb(float v)
 {

@@ -168,6 +168,11 @@ class Prims:
     def f(self, name):
         return getattr(self.lib, self.px + name)
 
+    def has(self, name):
+        """Whether the library exports this function (an oracle/_ref built from an older ref_harness.cc, kept
+        where the reference tree is absent, lacks the functions added since)."""
+        return hasattr(self.lib, self.px + name)
+
     def ri(self, which, bits, r):
         bits = np.ascontiguousarray(bits, np.uint32)
         r = np.ascontiguousarray(r, np.uint32)
@@ -262,7 +267,14 @@ def _tiles(self, w, h, bs, order, nthreads=1):
     return out[:4 * n].reshape(-1, 4)
 
 
-Prims.shirley, Prims.rgbe, Prims.tiles = _shirley, _rgbe, _tiles
+def _film_filter(self, name, dxdy):
+    """The film filter function `name` ("gauss" | "mitchell" | "lanczos", include/math/filter.h) at (dx, dy) pairs."""
+    if name == "lanczos" and self.px == "ref_":
+        name = "lanczos2"      # the reference's own name
+    return self.unary("filter_" + name, np.ascontiguousarray(dxdy, np.float32).reshape(-1), 1, 2)
+
+
+Prims.shirley, Prims.rgbe, Prims.tiles, Prims.film_filter = _shirley, _rgbe, _tiles, _film_filter
 
 
 def oracle_prims() -> Prims:

@@ -13,7 +13,7 @@
 //   src/math/random.cc             FastRandom::myseed_
 //   include/geometry/vector.h      Vec3 normalize / createCoordsSystem / reflectDir
 //   include/geometry/bound.h       Bound::cross (Smits slab test)
-//   include/math/filter.h          box / gauss filter kernels (film table entries)
+//   include/math/filter.h          box / gauss / mitchell / lanczos2 filter kernels (film table entries)
 //   include/color/color.h          Rgb::clampProportionalRgb, colour-space conversions, HSV
 //   include/image/image_buffers.h  the image buffer pixel types (texture storage quantisation)
 //   include/math/interpolation.h   cubicInterpolate (bicubic texture lookups)
@@ -165,6 +165,16 @@ void ref_mwc(uint32_t seed, int steps, double *out)
 void ref_filter_gauss(const float *dxdy, float *out, int n)
 {
 	for(int i = 0; i < n; ++i) out[i] = math::filter::gauss(dxdy[2 * i], dxdy[2 * i + 1]);
+}
+
+void ref_filter_mitchell(const float *dxdy, float *out, int n)
+{
+	for(int i = 0; i < n; ++i) out[i] = math::filter::mitchell(dxdy[2 * i], dxdy[2 * i + 1]);
+}
+
+void ref_filter_lanczos2(const float *dxdy, float *out, int n)
+{
+	for(int i = 0; i < n; ++i) out[i] = math::filter::lanczos2(dxdy[2 * i], dxdy[2 * i + 1]);
 }
 
 void ref_round_to_int(const double *v, int *out, int n)

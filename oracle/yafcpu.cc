@@ -3679,6 +3679,8 @@ void yc_mwc(uint32_t seed, int steps, double *out)
 	for(int i = 0; i < steps; ++i) out[i] = m();
 }
 void yc_filter_gauss(const float *dxdy, float *out, int n) { for(int i = 0; i < n; ++i) out[i] = filterGauss(dxdy[2 * i], dxdy[2 * i + 1]); }
+void yc_filter_mitchell(const float *dxdy, float *out, int n) { for(int i = 0; i < n; ++i) out[i] = filterMitchell(dxdy[2 * i], dxdy[2 * i + 1]); }
+void yc_filter_lanczos(const float *dxdy, float *out, int n) { for(int i = 0; i < n; ++i) out[i] = filterLanczos(dxdy[2 * i], dxdy[2 * i + 1]); }
 void yc_round_to_int(const double *v, int *out, int n) { for(int i = 0; i < n; ++i) out[i] = roundToInt(v[i]); }
 void yc_floor_to_int(const double *v, int *out, int n) { for(int i = 0; i < n; ++i) out[i] = floorToInt(v[i]); }
 void yc_clamp_proportional(const float *rgb, float max_value, float *out, int n)

@@ -259,6 +259,8 @@ void yc_normalize(const float *in, float *out, int n);
 void yc_bound_cross(const float *box, const float *ray, float *out, int n);
 void yc_mwc(uint32_t seed, int steps, double *out);
 void yc_filter_gauss(const float *dxdy, float *out, int n);
+void yc_filter_mitchell(const float *dxdy, float *out, int n);
+void yc_filter_lanczos(const float *dxdy, float *out, int n);
 void yc_round_to_int(const double *v, int *out, int n);
 void yc_floor_to_int(const double *v, int *out, int n);
 void yc_clamp_proportional(const float *rgb, float max_value, float *out, int n);

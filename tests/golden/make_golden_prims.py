@@ -7,6 +7,9 @@ computed by the reference code itself (include/sampler/sample.h, src/sampler/hal
 include/math/math.h FAST_MATH/FAST_TRIG, include/math/random.h, include/geometry/vector.h,
 include/geometry/bound.h, include/math/filter.h, include/color/color.h).
 The CPU oracle and the device numerics are pinned against this file (tests/test_oracle_golden.py).
+    python tests/golden/make_golden_prims.py filters
+writes only tests/golden/prims_filters.npz: the reference's mitchell and lanczos2 film filter functions, against
+which the oracle's and the product's host restatements are pinned (tests/test_oracle_golden.py).
 """
 import os
 import sys
@@ -107,5 +110,65 @@ def main():
     print("wrote", OUT2, os.path.getsize(OUT2), "bytes,", len(g2), "arrays")
 
 
+# ---- film filter functions (include/math/filter.h mitchell / lanczos2): tests/golden/prims_filters.npz ----
+OUT_FILTERS = os.path.join(os.path.dirname(OUT), "prims_filters.npz")
+FILTER_RANDOM_N, FILTER_RANDOM_SEED = 100000, 0x66696c6d
+
+
+def splitmix_points(n, seed):
+    """n points of [0, 1.5)^2 (float32) from splitmix64 in integer arithmetic: the same on every machine, so the
+    fixture stores the reference's outputs for them and only a checksum of the points themselves."""
+    with np.errstate(over="ignore"):
+        z = (np.arange(2 * n, dtype=np.uint64) + np.uint64(seed)) * np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z ^= z >> np.uint64(31)
+    u = (z >> np.uint64(40)).astype(np.float32) * np.float32(2.0 ** -24)    # 24 bits: exact in float32
+    return (u * np.float32(1.5)).reshape(n, 2)
+
+
+def filter_points():
+    """The recorded inputs other than the random ones: the film table's 256 points as imagefilm.cc:153-160
+    computes them, (0, 0) (lanczos2's x == 0 branch), and points on and to both sides of r = 0.5 and r = 1
+    (mitchell's branches x = 1 and x = 2; lanczos2's lobes): along both axes, the diagonal and the exact
+    3-4-5 points, each coordinate with its float neighbours up to 3 steps away."""
+    scale = np.float32(1.0) / np.float32(16.0)
+    k = np.arange(16, dtype=np.float32)
+    c = (k + np.float32(.5)) * scale
+    table = np.stack(np.meshgrid(c, c, indexing="xy"), -1).reshape(-1, 2)       # row y, column x: (x, y)
+    edge = []
+    for r in (0.5, 1.0):
+        for px, py in ((r, 0.0), (0.0, r), (r * 0.6, r * 0.8), (r * 0.8, r * 0.6), (r / np.sqrt(2.0), r / np.sqrt(2.0))):
+            for sx in range(-3, 4):
+                for sy in range(-3, 4):
+                    p = np.array([px, py], np.float32)
+                    for axis, steps in ((0, sx), (1, sy)):
+                        for _ in range(abs(steps)):
+                            p[axis] = np.nextafter(p[axis], np.float32(np.inf if steps > 0 else -np.inf))
+                    edge.append(p)
+    edge = np.unique(np.array(edge, np.float32), axis=0)
+    return np.concatenate([table, np.zeros((1, 2), np.float32), edge]).astype(np.float32)
+
+
+def points_checksum(p):
+    return np.array([int(np.ascontiguousarray(p, np.float32).view(np.uint32).astype(np.uint64).sum())], np.uint64)
+
+
+def main_filters():
+    r = O.ref_prims()
+    if r is None:
+        sys.exit("oracle/_ref not built (needs the reference tree): the committed prims_filters.npz is used as is")
+    g = {"points": filter_points(), "random_n": np.array([FILTER_RANDOM_N]), "random_seed": np.array([FILTER_RANDOM_SEED])}
+    rnd = splitmix_points(FILTER_RANDOM_N, FILTER_RANDOM_SEED)
+    g["random_checksum"] = points_checksum(rnd)
+    g["random_head"] = rnd[:16]
+    for name in ("mitchell", "lanczos"):
+        g[name] = r.film_filter(name, g["points"])
+        g[name + "_random"] = r.film_filter(name, rnd)
+    np.savez_compressed(OUT_FILTERS, **g)
+    print("wrote", OUT_FILTERS, os.path.getsize(OUT_FILTERS), "bytes,", len(g), "arrays")
+
+
 if __name__ == "__main__":
-    main()
+    # "filters": only prims_filters.npz (prims.npz and prims_r02.npz stay as committed)
+    main_filters() if sys.argv[1:] == ["filters"] else main()

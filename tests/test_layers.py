@@ -126,11 +126,14 @@ def test_layers_exact_per_pixel(product, oracle_built, case):
 
 
 # ---- 2. film arithmetic under real filtering ----
-def _filtered(spec):
-    return spec.with_render(width=41, height=23, aa_samples=5, filter_type="gauss", aa_pixelwidth=1.5, tile_size=8)
+def _filtered(spec, filt=("gauss", 1.5)):
+    return spec.with_render(width=41, height=23, aa_samples=5, filter_type=filt[0], aa_pixelwidth=filt[1], tile_size=8)
 
 
 def _flat_scene(kind):
+    if kind == "plain-mitchell4":
+        # filterw clamped at 4.0: k_layer_film's generic window at 8 x 8 (reach 4 forward, 3 back), a signed table
+        return _filtered(_flat_scene("plain"), ("mitchell", 4.0))
     if kind == "instanced":
         s = scenes.cornell_instanced(41, 23, spp=5, integrator="directlighting")
         objs = [dataclasses.replace(o, object_index=k) for o, k in zip(s.objects, (2, 0, 5, 1, 8, 13))]   # the base cube: 13
@@ -143,7 +146,7 @@ def _flat_scene(kind):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind", ["plain", "instanced"])
+@pytest.mark.parametrize("kind", ["plain", "instanced", "plain-mitchell4"])
 def test_index_layers_through_the_film(product, oracle_built, kind):
     spec = _flat_scene(kind)
     flat = scenes.flatten_instances(spec) if spec.instances else spec

@@ -1,6 +1,6 @@
 """Pin the CPU oracle (oracle/yafcpu.cc) against the reference's own code:
-(1) the committed golden vectors of tests/golden/prims.npz (made by make_golden_prims.py from
-    oracle/_ref, i.e. the reference sources compiled here), always;
+(1) the committed golden vectors of tests/golden/prims.npz, prims_r02.npz and prims_filters.npz (made by
+    make_golden_prims.py from oracle/_ref, i.e. the reference sources compiled here), always;
 (2) the live reference building blocks on fresh random inputs, when oracle/_ref is built."""
 import os
 import sys
@@ -136,6 +136,55 @@ def test_live_reference_round2_random_inputs(o, oracle_built):
     assert same(o.rgbe(b), r.rgbe(b))
     for w, h, bs in [(37, 29, 5), (640, 480, 32), (1, 1, 16)]:
         assert np.array_equal(o.tiles(w, h, bs, "linear"), r.tiles(w, h, bs, "linear"))
+
+
+# ---- film filter functions (tests/golden/prims_filters.npz: include/math/filter.h mitchell, lanczos2 at the film
+# table's 256 points, (0, 0), the float neighbourhoods of r = 0.5 and r = 1, and 10^5 points of [0, 1.5)^2) ----
+GF = np.load(os.path.join(HERE, "golden", "prims_filters.npz"))
+
+
+def filter_random_points():
+    """The fixture's random inputs, regenerated (integer arithmetic) and checked against its checksum."""
+    sys.path.insert(0, os.path.join(HERE, "golden"))
+    import make_golden_prims as M
+    rnd = M.splitmix_points(int(GF["random_n"][0]), int(GF["random_seed"][0]))
+    assert np.array_equal(M.points_checksum(rnd), GF["random_checksum"]) and same(rnd[:16], GF["random_head"])
+    assert len(rnd) == 100000 and rnd.min() >= 0 and rnd.max() < 1.5
+    return rnd
+
+
+def test_filter_fixture_covers_the_branches():
+    p = GF["points"].astype(np.float64)
+    r = np.hypot(p[:, 0], p[:, 1])
+    assert len(p) >= 256 + 1 + 100 and (p == 0).all(1).any()
+    for edge in (0.5, 1.0):
+        near = np.abs(r - edge) < 1e-6
+        assert (r[near] < edge).any() and (r[near] > edge).any()
+    assert (GF["mitchell"] < 0).any() and (GF["lanczos"] < 0).any()      # signed lobes
+    assert (GF["mitchell_random"] < 0).sum() > 1000 and (GF["lanczos_random"] < 0).sum() > 1000
+
+
+@pytest.mark.parametrize("name", ["mitchell", "lanczos"])
+def test_film_filter_signed(o, name):
+    assert same(o.film_filter(name, GF["points"]), GF[name])
+    assert same(o.film_filter(name, filter_random_points()), GF[name + "_random"])
+
+
+def test_live_reference_film_filters_random_inputs(o, oracle_built):
+    r = oracle_built.ref_prims()
+    if r is None:
+        pytest.skip("oracle/_ref not built (reference tree absent): golden vectors above still pin the oracle")
+    rng = np.random.default_rng(4242)
+    d = np.concatenate([rng.uniform(-1.5, 1.5, (100000, 2)), rng.uniform(-0.01, 0.01, (1000, 2)),
+                        rng.uniform(-2.5, 2.5, (10000, 2))]).astype(np.float32)
+    assert same(o.film_filter("gauss", d), r.film_filter("gauss", d))
+    if not (r.has("filter_mitchell") and r.has("filter_lanczos2")):
+        # an oracle/_ref kept from before ref_harness.cc had these two (make ref rebuilds it only where the
+        # reference tree is present)
+        pytest.skip("oracle/_ref predates ref_filter_mitchell / ref_filter_lanczos2 and was not rebuilt (reference tree "
+                    "absent): gauss checked; golden vectors above still pin mitchell and lanczos")
+    for name in ("mitchell", "lanczos"):
+        assert same(o.film_filter(name, d), r.film_filter(name, d)), name
 
 
 # ---- texturing building blocks (tests/golden/tex_prims.npz, made by make_golden_tex.py from the

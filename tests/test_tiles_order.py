@@ -12,26 +12,16 @@ Parity: the film equals the oracle's film of the same order (<= 4 ULP, gauss fil
 sample splats across tile borders).  Callbacks: one highlightArea + the tile's putPixels + one
 flushArea per tile in the order, area ids 0..n-1; a putPixel shows the pixel as the one-thread render
 does when its tile finishes — equal to the final value wherever every footprint source's tile
-finished no later; the final flush shows the film.
+finished no later; the final flush shows the film.  (With a backward-reaching filter no order settles every
+pixel: tests/test_film_filters.py::test_partial_film_with_backward_reach checks those values tile by tile.)
 """
 import dataclasses
 
 import numpy as np
 import pytest
 
+from filmlib import tile_list as tile_order   # (x0, y0, x1, y1) in render order — the restatement of imagesplitter.cc
 from libyafaray_amd import scenes
-
-
-def tile_order(W, H, ts, order):
-    """The tile list in render order, as (x0, y0, x1, y1) — the restatement of imagesplitter.cc."""
-    ntx, nty = (W + ts - 1) // ts, (H + ts - 1) // ts
-    ids = list(range(ntx * nty))
-    if order == "centre":
-        key = lambda i: ((i % ntx) * ts - W // 2) ** 2 + ((i // ntx) * ts - H // 2) ** 2
-        ids = sorted(ids, key=key)   # Python's sort is stable: ties keep linear order
-    elif order != "linear":
-        raise ValueError(order)
-    return [((i % ntx) * ts, (i // ntx) * ts, min(W, (i % ntx) * ts + ts), min(H, (i // ntx) * ts + ts)) for i in ids]
 
 
 def ulp_diff(a, b):
