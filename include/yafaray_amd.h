@@ -107,6 +107,29 @@ YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_traceQueued(yafaray_Interface_t 
                                                             const float *shadow_rays, int n_shadow, int n_seg, int part, float *t, int *prims,
                                                             int *occluded, unsigned long long *counted);
 
+/* Test infrastructure (LIBYAFARAY_AMD_1.10): final gathering's radiance-point thinning on caller-supplied points.
+ * pos, nrm: n x 3 floats; maxrad: the squared distance below which (strictly) two points whose normals face the
+ * same side (dot > 0) are related.  kept (n entries of capacity) receives the kept indices in ascending order,
+ * *n_kept their count.  mode 0: what a render does — the GPU rounds, or the host twin where the GPU refuses the
+ * point set (its dense cell grid too large) or YAFARAY_AMD_FG_THIN=host asks for it; *rounds = the GPU's round
+ * count, -1 after the host twin.  mode 1: the GPU only; false with a lastError text where it refuses.  mode 2:
+ * the host twin only (no device needed).  Needs no scene; modes 0 and 1 run on the interface's device and stream
+ * and reuse its thinning scratch from call to call. */
+YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_thinRadPoints(yafaray_Interface_t *interface, const float *pos, const float *nrm, int n,
+                                                              float maxrad, int mode, unsigned int *kept, int *n_kept, int *rounds);
+/* Test infrastructure (LIBYAFARAY_AMD_1.10): adaptive anti-aliasing's nextPass on a caller-supplied accumulated film.
+ * accum: width x height x 4 floats (unnormalised), weights: width x height; tile: the tile size of the visiting
+ * order; detect_color_noise ... variance_pixels: the AA noise parameters (dark_type 0 none, 1 linear, 2 curve);
+ * rows [ry0, ry1): the band whose resampled pixels are listed.  flags (width x height bytes) receives the whole
+ * film's resample flags, *count their number, plist (width x height entries of capacity) the flagged pixels
+ * (y * width + x) of the band in visiting order, *local_count how many.  False (and a logged error, nothing
+ * launched) for width, height or tile <= 0 or a row range outside 0 <= ry0 <= ry1 <= height.  Needs no scene. */
+YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_aaNextPass(yafaray_Interface_t *interface, const float *accum, const float *weights, int width,
+                                                           int height, int tile, int detect_color_noise, int dark_type, float dark_factor,
+                                                           int variance_edge, int variance_pixels, float threshold, int ry0, int ry1,
+                                                           unsigned char *flags, unsigned int *plist, unsigned int *count,
+                                                           unsigned int *local_count);
+
 /* The built scene's primitives [first, first + count) in creation order (instances expanded, as the
  * ray queries number them), as the device holds them: verts9 the three world-space vertices, ng3 the
  * geometric normal, vnormals9 the three vertex normals (the geometric normal where the primitive is

@@ -140,6 +140,11 @@ def lib():
             "yafaray_amd_traceShadow": (b, [vp, C.POINTER(C.c_float), i, C.POINTER(C.c_int)]),
             "yafaray_amd_traceQueued": (b, [vp, C.POINTER(C.c_float), i, C.POINTER(C.c_float), i, i, i, C.POINTER(C.c_float),
                                             C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]),
+            "yafaray_amd_thinRadPoints": (b, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i, f, i, C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+            "yafaray_amd_aaNextPass": (b, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i, i, i, i, i, f, i, i, f, i, i,
+                                           C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_uint32)]),
             "yafaray_amd_getFilm": (b, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
             "yafaray_amd_getFilmDevice": (b, [vp, vp, i, i]),
             "yafaray_amd_getLayerCount": (i, [vp]),
@@ -463,6 +468,45 @@ class Interface:
                                               o.ctypes.data_as(C.POINTER(C.c_int)), counted):
             raise RuntimeError("traceQueued failed: " + self.last_error())
         return t[:nc], p[:nc], o[:ns], int(counted[0]), int(counted[1])
+
+    THIN_MODES = {"render": 0, "gpu": 1, "host": 2}
+
+    def thin_rad_points(self, pos, nrm, maxrad, mode="render"):
+        """Test infrastructure (yafaray_amd_thinRadPoints): final gathering's radiance-point thinning of (n, 3)
+        positions and normals.  mode "render": the render's choice (GPU, host twin where the GPU refuses),
+        "gpu" / "host": one of them alone.  Returns (kept indices uint32, rounds; -1 after the host twin)."""
+        fp = C.POINTER(C.c_float)
+        p = np.ascontiguousarray(pos, np.float32).reshape(-1)
+        q = np.ascontiguousarray(nrm, np.float32).reshape(-1)
+        n = len(p) // 3
+        assert len(q) == len(p) == 3 * n
+        kept = np.zeros(max(n, 1), np.uint32)
+        nk, rounds = C.c_int(0), C.c_int(0)
+        if not self.L.yafaray_amd_thinRadPoints(self.h, p.ctypes.data_as(fp), q.ctypes.data_as(fp), n, float(np.float32(maxrad)),
+                                                self.THIN_MODES[mode], kept.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(nk),
+                                                C.byref(rounds)):
+            raise RuntimeError("thinRadPoints failed: " + self.last_error())
+        return kept[:nk.value].copy(), rounds.value
+
+    def aa_next_pass(self, accum, weights, tile, threshold, detect_color_noise=False, dark_type=0, dark_factor=0.0, variance_edge=10,
+                     variance_pixels=0, ry0=0, ry1=None):
+        """Test infrastructure (yafaray_amd_aaNextPass): adaptive AA's nextPass on an accumulated film ((H, W, 4)
+        accumulators, (H, W) weights).  Returns (flags (H, W) uint8, plist of the rows [ry0, ry1) in visiting
+        order, count of the whole film, local_count)."""
+        fp = C.POINTER(C.c_float)
+        w = np.ascontiguousarray(weights, np.float32)
+        H, W = w.shape
+        a = np.ascontiguousarray(accum, np.float32).reshape(H, W, 4)
+        flags = np.zeros((H, W), np.uint8)
+        plist = np.zeros(max(H * W, 1), np.uint32)
+        count, local = C.c_uint32(0), C.c_uint32(0)
+        if not self.L.yafaray_amd_aaNextPass(self.h, a.ctypes.data_as(fp), w.ctypes.data_as(fp), W, H, int(tile), int(bool(detect_color_noise)),
+                                             int(dark_type), float(dark_factor), int(variance_edge), int(variance_pixels),
+                                             float(np.float32(threshold)), int(ry0), int(H if ry1 is None else ry1),
+                                             flags.ctypes.data_as(C.POINTER(C.c_uint8)), plist.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                             C.byref(count), C.byref(local)):
+            raise RuntimeError("aaNextPass failed: " + self.last_error())
+        return flags, plist[:local.value].copy(), count.value, local.value
 
 
 

@@ -522,6 +522,36 @@ yafaray_bool_t yafaray_amd_traceQueued(yafaray_Interface_t *interface, const flo
 	return YAFARAY_BOOL_TRUE;
 }
 
+// (the two selection passes need no scene description: a bare interface gets an empty scene to hold the renderer)
+static GpuRenderer *rendererOf(yafaray_Interface_t *interface)
+{
+	Interface *it = I(interface);
+	if(!it->scene) it->scene.reset(new Scene(it->logger));
+	return it->scene->gpu();
+}
+
+yafaray_bool_t yafaray_amd_thinRadPoints(yafaray_Interface_t *interface, const float *pos, const float *nrm, int n, float maxrad, int mode,
+                                         unsigned int *kept, int *n_kept, int *rounds)
+{
+	return rendererOf(interface)->thinRadPointsHost(pos, nrm, n, maxrad, mode, kept, n_kept, rounds) ? YAFARAY_BOOL_TRUE : YAFARAY_BOOL_FALSE;
+}
+
+yafaray_bool_t yafaray_amd_aaNextPass(yafaray_Interface_t *interface, const float *accum, const float *weights, int width, int height, int tile,
+                                      int detect_color_noise, int dark_type, float dark_factor, int variance_edge, int variance_pixels,
+                                      float threshold, int ry0, int ry1, unsigned char *flags, unsigned int *plist, unsigned int *count,
+                                      unsigned int *local_count)
+{
+	DevAaParams prm{};
+	prm.detect_color_noise = detect_color_noise;
+	prm.dark_type = dark_type;
+	prm.dark_factor = dark_factor;
+	prm.variance_edge = variance_edge;
+	prm.variance_pixels = variance_pixels;
+	return rendererOf(interface)->aaNextPassHost(accum, weights, width, height, tile, prm, threshold, ry0, ry1, flags, plist, count, local_count)
+	           ? YAFARAY_BOOL_TRUE
+	           : YAFARAY_BOOL_FALSE;
+}
+
 yafaray_bool_t yafaray_amd_getFilm(const yafaray_Interface_t *interface, float *rgba, float *weights)
 {
 	const Interface *it = I(interface);

@@ -463,7 +463,7 @@ extern "C" hipError_t yafamd_thin_rad_points(const float4 *pos, const float4 *nr
 		THCHECK(hipStreamSynchronize(st));
 		std::swap(sin, sout);
 		++rounds;
-		if(rounds > 1000000) return hipErrorUnknown;   // cannot happen: every round decides the lowest undecided point
+		if((uint32_t)rounds > n) return hipErrorUnknown;   // cannot happen: every round decides the lowest undecided point
 	}
 	// the final states are in `sin` (cell order): back to shooting order in `sout`, then the kept indices
 	hipLaunchKernelGGL(k_thin_unsort, blocks, dim3(256), 0, st, sin, S.order.as<uint32_t>(), n, sout);

@@ -1493,6 +1493,49 @@ const void *GpuRenderer::mapView(int which, int f, const void *photon_order) con
 	return f == 0 ? d_->kd_pos[which].p : f == 1 ? d_->kd_dir[which].p : d_->kd_colb[which].p;
 }
 
+// The radiance points' thinning, GPU or host twin: n points (float4 positions / normals on the device) -> the kept
+// indices in kept_dev (device, n entries of capacity), ascending.  The render's choice: the GPU (fgthin.hip) unless
+// YAFARAY_AMD_FG_THIN=host forces the host twin (tests compare both), and the host twin where the GPU refuses a
+// grid too large for a dense cell table.  gpu_only: the GPU whatever the environment says, and such a refusal
+// fails.  rounds: the GPU's round count, -1 after the host twin.
+bool GpuRenderer::thinPoints(const void *pos_dev, const void *nrm_dev, uint32_t n, float maxrad, bool gpu_only, void *kept_dev, uint32_t &nk,
+                             int &rounds)
+{
+	Impl &d = *d_;
+	nk = 0;
+	rounds = 0;
+	const char *thin_env = std::getenv("YAFARAY_AMD_FG_THIN");
+	const bool host_thin = !gpu_only && thin_env && std::string(thin_env) == "host";
+	if(!host_thin)
+	{
+		const hipError_t te = yafamd_thin_rad_points((const float4 *)pos_dev, (const float4 *)nrm_dev, n, maxrad, (uint32_t *)kept_dev, &nk,
+		                                             &rounds, d.stream, &d.thin_scratch);
+		if(te != hipErrorNotSupported)
+		{
+			HIPCHECK(te);
+			return true;
+		}
+		if(gpu_only)
+		{
+			log_.error("GPU: thinning: the dense cell grid of these points is too large for the GPU (the host twin serves them)");
+			return false;
+		}
+	}
+	std::vector<float4> pos(n), nrm(n);
+	if(n)
+	{
+		HIPCHECK(hipMemcpyAsync(pos.data(), pos_dev, (size_t)n * 16, hipMemcpyDeviceToHost, d.stream));
+		HIPCHECK(hipMemcpyAsync(nrm.data(), nrm_dev, (size_t)n * 16, hipMemcpyDeviceToHost, d.stream));
+	}
+	HIPCHECK(hipStreamSynchronize(d.stream));
+	const std::vector<uint32_t> kept = eliminateRadPoints(pos, nrm, maxrad);
+	nk = (uint32_t)kept.size();
+	if(nk) HIPCHECK(hipMemcpyAsync(kept_dev, kept.data(), (size_t)nk * 4, hipMemcpyHostToDevice, d.stream));
+	HIPCHECK(hipStreamSynchronize(d.stream));
+	rounds = -1;
+	return true;
+}
+
 // Final gathering's radiance map (integrator_photon_mapping.cc:540-591): the radiance points shootMap
 // compacted are thinned on the host (eliminateRadPoints), pre-gathered on the GPU (k_pregather) and
 // the point kd-tree of the radiance map is built like the photon maps'.
@@ -1505,28 +1548,9 @@ bool GpuRenderer::buildRadianceMap(RenderParams &rp)
 	const auto tr0 = std::chrono::steady_clock::now();
 	const float maxrad = 0.01f * pm.radius2;   // :568 (used as a squared distance)
 	if(!ensure(log_, d.rad_kept, (size_t)std::max(1u, nr) * 4)) return false;
-	// thinning on the GPU (fgthin.hip); the host twin serves grids too large for a dense cell table
 	uint32_t nk = 0;
 	int rounds = 0;
-	// YAFARAY_AMD_FG_THIN=host forces the host twin (tests compare both)
-	const char *thin_env = std::getenv("YAFARAY_AMD_FG_THIN");
-	const bool host_thin = thin_env && std::string(thin_env) == "host";
-	const hipError_t te = host_thin ? hipErrorNotSupported
-	                                : yafamd_thin_rad_points((const float4 *)d.radc_a.p, (const float4 *)d.radc_b.p, nr, maxrad,
-	                                                         (uint32_t *)d.rad_kept.p, &nk, &rounds, d.stream, &d.thin_scratch);
-	if(te == hipErrorNotSupported)
-	{
-		std::vector<float4> pos(nr), nrm(nr);
-		HIPCHECK(hipMemcpyAsync(pos.data(), d.radc_a.p, (size_t)nr * 16, hipMemcpyDeviceToHost, d.stream));
-		HIPCHECK(hipMemcpyAsync(nrm.data(), d.radc_b.p, (size_t)nr * 16, hipMemcpyDeviceToHost, d.stream));
-		HIPCHECK(hipStreamSynchronize(d.stream));
-		const std::vector<uint32_t> kept = eliminateRadPoints(pos, nrm, maxrad);
-		nk = (uint32_t)kept.size();
-		if(nk) HIPCHECK(hipMemcpyAsync(d.rad_kept.p, kept.data(), (size_t)nk * 4, hipMemcpyHostToDevice, d.stream));
-		HIPCHECK(hipStreamSynchronize(d.stream));
-		rounds = -1;
-	}
-	else HIPCHECK(te);
+	if(!thinPoints(d.radc_a.p, d.radc_b.p, nr, maxrad, false, d.rad_kept.p, nk, rounds)) return false;
 	stats_.radiance_points = nr;
 	stats_.radiance_photons = nk;
 	stats_.fg_thin_rounds = rounds;
@@ -3690,6 +3714,91 @@ bool GpuRenderer::traceRaysQueued(const float *closest, int n_closest, const flo
 		counted[0] = counted[1] = 0;
 		for(const DevStats &b : per_block) { counted[0] += b.closest_rays; counted[1] += b.shadow_rays; }
 	}
+	return true;
+}
+
+// Test infrastructure (yafaray_amd_thinRadPoints): caller-supplied radiance points (xyz positions and normals)
+// through thinPoints, the selection buildRadianceMap makes, on this renderer's stream and thinning scratch (so
+// consecutive calls reuse it, as consecutive frames do); THIN_HOST runs the host twin alone and touches no
+// device.  kept: n entries of capacity.
+bool GpuRenderer::thinRadPointsHost(const float *pos3, const float *nrm3, int n, float maxrad, int mode, uint32_t *kept, int *n_kept, int *rounds)
+{
+	if(n < 0 || (n && (!pos3 || !nrm3 || !kept)) || !n_kept || !rounds) { log_.error("GPU: thinRadPoints: bad arrays"); return false; }
+	if(mode != THIN_RENDER && mode != THIN_GPU && mode != THIN_HOST) { log_.error("GPU: thinRadPoints: bad mode"); return false; }
+	std::vector<float4> pos((size_t)n), nrm((size_t)n);
+	for(int i = 0; i < n; ++i)
+	{
+		pos[i] = make_float4(pos3[3 * (size_t)i], pos3[3 * (size_t)i + 1], pos3[3 * (size_t)i + 2], 0.f);
+		nrm[i] = make_float4(nrm3[3 * (size_t)i], nrm3[3 * (size_t)i + 1], nrm3[3 * (size_t)i + 2], 0.f);
+	}
+	if(mode == THIN_HOST)
+	{
+		const std::vector<uint32_t> k = eliminateRadPoints(pos, nrm, maxrad);
+		std::copy(k.begin(), k.end(), kept);
+		*n_kept = (int)k.size();
+		*rounds = -1;
+		return true;
+	}
+	if(!ready()) return false;
+	DeviceGuard guard(device_);
+	Buf b_pos, b_nrm, b_kept;
+	uint32_t nk = 0;
+	int r = 0;
+	bool ok = allocCopy(log_, b_pos, pos.data(), pos.size()) && allocCopy(log_, b_nrm, nrm.data(), nrm.size()) &&
+	          ensure(log_, b_kept, (size_t)std::max(1, n) * 4) &&
+	          thinPoints(b_pos.p, b_nrm.p, (uint32_t)n, maxrad, mode == THIN_GPU, b_kept.p, nk, r);
+	if(ok && nk > (uint32_t)n)
+	{
+		log_.error("GPU: thinRadPoints: more points kept than given");
+		ok = false;
+	}
+	if(ok && nk) ok = hipMemcpy(kept, b_kept.p, (size_t)nk * 4, hipMemcpyDeviceToHost) == hipSuccess;
+	for(Buf *b : {&b_pos, &b_nrm, &b_kept}) b->release();
+	if(!ok) return false;
+	*n_kept = (int)nk;
+	*rounds = r;
+	return true;
+}
+
+// Test infrastructure (yafaray_amd_aaNextPass): a caller-supplied accumulated film through the production
+// yafamd_aa_next_pass (the call adaptivePasses makes) on this renderer's stream.  flags: W * H bytes; plist: W * H
+// entries of capacity, *local_count of them written.
+bool GpuRenderer::aaNextPassHost(const float *accum, const float *weights, int W, int H, int tile, const DevAaParams &prm, float threshold,
+                                 int ry0, int ry1, uint8_t *flags, uint32_t *plist, uint32_t *count, uint32_t *local_count)
+{
+	if(!ready()) return false;
+	DeviceGuard guard(device_);
+	Impl &d = *d_;
+	if(W <= 0 || H <= 0 || tile <= 0 || (uint64_t)W * (uint64_t)H > (1ull << 28))
+	{
+		log_.error("GPU: aaNextPass: width, height and tile size must be positive (at most 2^28 pixels)");
+		return false;
+	}
+	if(ry0 < 0 || ry1 > H || ry0 > ry1) { log_.error("GPU: aaNextPass: the row range must satisfy 0 <= ry0 <= ry1 <= height"); return false; }
+	if(!accum || !weights || !flags || !plist || !count || !local_count) { log_.error("GPU: aaNextPass: bad arrays"); return false; }
+	const size_t n = (size_t)W * H;
+	Buf b_acc, b_w, b_flags, b_plist;
+	uint32_t c = 0, lc = 0;
+	bool ok = allocCopy(log_, b_acc, accum, 4 * n) && allocCopy(log_, b_w, weights, n) && ensure(log_, b_flags, n) &&
+	          ensure(log_, b_plist, n * 4);
+	if(ok)
+	{
+		ok = yafamd_aa_next_pass((const float4 *)b_acc.p, (const float *)b_w.p, W, H, tile, &prm, threshold, (uint8_t *)b_flags.p,
+		                         (uint32_t *)b_plist.p, &c, ry0, ry1, &lc, d.stream) == hipSuccess &&
+		     hipStreamSynchronize(d.stream) == hipSuccess;
+		if(!ok) log_.error("GPU: aaNextPass: launch failed");
+		if(ok && (lc > n || c > n))
+		{
+			log_.error("GPU: aaNextPass: more pixels listed than the film has");
+			ok = false;
+		}
+		ok = ok && hipMemcpy(flags, b_flags.p, n, hipMemcpyDeviceToHost) == hipSuccess &&
+		     (lc == 0 || hipMemcpy(plist, b_plist.p, (size_t)lc * 4, hipMemcpyDeviceToHost) == hipSuccess);
+	}
+	for(Buf *b : {&b_acc, &b_w, &b_flags, &b_plist}) b->release();
+	if(!ok) return false;
+	*count = c;
+	*local_count = lc;
 	return true;
 }
 

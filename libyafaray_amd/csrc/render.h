@@ -243,6 +243,14 @@ class GpuRenderer
 		// test infrastructure: the rays through the production k_trace launch (queues of n_seg ragged segments; part = TRACE_*)
 		bool traceRaysQueued(const float *closest, int n_closest, const float *shadow, int n_shadow, int n_seg, int part,
 		                     bool trace_stats, float *t, int *prim, int *occluded, uint64_t *counted);
+		// the radiance points' thinning: the GPU rounds, or their host twin where the GPU refuses (gpu_only: fail there)
+		bool thinPoints(const void *pos_dev, const void *nrm_dev, uint32_t n, float maxrad, bool gpu_only, void *kept_dev, uint32_t &nk, int &rounds);
+		// test infrastructure: host arrays through thinPoints (mode THIN_HOST: through the host twin alone, no device
+		// needed) / through the production yafamd_aa_next_pass
+		enum : int { THIN_RENDER = 0, THIN_GPU = 1, THIN_HOST = 2 };
+		bool thinRadPointsHost(const float *pos3, const float *nrm3, int n, float maxrad, int mode, uint32_t *kept, int *n_kept, int *rounds);
+		bool aaNextPassHost(const float *accum, const float *weights, int W, int H, int tile, const DevAaParams &prm, float threshold, int ry0,
+		                    int ry1, uint8_t *flags, uint32_t *plist, uint32_t *count, uint32_t *local_count);
 		bool buildPhotonMap(RenderParams &rp);
 		bool buildRadianceMap(RenderParams &rp);
 		bool shootMap(RenderParams &rp, const PhotonSet &L, uint32_t N, int bounces, int which, uint32_t &n_out, int &depth_out);

@@ -274,7 +274,25 @@ def _film_filter(self, name, dxdy):
     return self.unary("filter_" + name, np.ascontiguousarray(dxdy, np.float32).reshape(-1), 1, 2)
 
 
+def _color_difference(self, ab, use_rgb):
+    """Rgba::colorDifference of (n, 8) colour pairs (this, color_2), with / without the r, g, b, a components."""
+    ab = np.ascontiguousarray(ab, np.float32).reshape(-1)
+    out = np.empty(len(ab) // 8, np.float32)
+    self.f("color_difference")(_p(ab, C.c_float), C.c_int(1 if use_rgb else 0), _p(out, C.c_float), C.c_int(len(out)))
+    return out
+
+
+def _normalized(self, cw):
+    """Rgba::normalized of (n, 5) rows (r, g, b, a, weight)."""
+    return self.unary("normalized", np.ascontiguousarray(cw, np.float32).reshape(-1), 4, 5).reshape(-1, 4)
+
+
+def _abscol2bri(self, rgb):
+    return self.unary("abscol2bri", np.ascontiguousarray(rgb, np.float32).reshape(-1), 1, 3)
+
+
 Prims.shirley, Prims.rgbe, Prims.tiles, Prims.film_filter = _shirley, _rgbe, _tiles, _film_filter
+Prims.color_difference, Prims.normalized, Prims.abscol2bri = _color_difference, _normalized, _abscol2bri
 
 
 def oracle_prims() -> Prims:
@@ -293,6 +311,54 @@ def film_table(filter_name: str, filter_size: float):
     lib.yc_film_table(C.c_int(FILTERS[filter_name]), C.c_float(filter_size), _p(tab, C.c_float), C.byref(fw),
                       C.byref(ts))
     return tab, fw.value, ts.value
+
+
+def dark_threshold_curve(b):
+    """The oracle's restatement of ImageFilm::darkThresholdCurveInterpolate (imagefilm.cc:799-815)."""
+    return oracle_prims().unary("dark_threshold_curve", np.ascontiguousarray(b, np.float32))
+
+
+def thin_rad_points(pos, nrm, maxrad):
+    """Final gathering's radiance-point thinning (yc_thin_rad_points, the body the oracle's render runs): the
+    kept indices of (n, 3) positions / normals, ascending."""
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1)
+    nrm = np.ascontiguousarray(nrm, np.float32).reshape(-1)
+    n = len(pos) // 3
+    kept = np.empty(max(n, 1), np.uint32)
+    lib = oracle_lib()
+    lib.yc_thin_rad_points.restype = C.c_int
+    nk = lib.yc_thin_rad_points(_p(pos, C.c_float), _p(nrm, C.c_float), C.c_int(n), C.c_float(maxrad), _p(kept, C.c_uint32))
+    return kept[:nk].copy()
+
+
+def aa_next_pass(accum, weights, threshold, detect_color_noise=False, dark_type=0, dark_factor=0.0, variance_edge=10,
+                 variance_pixels=0):
+    """ImageFilm::nextPass's resample flags ((H, W) uint8) of an accumulated film ((H, W, 4), (H, W)): the
+    sequential scatter of the reference (yc_aa_next_pass, the body the oracle's adaptive render runs)."""
+    w = np.ascontiguousarray(weights, np.float32)
+    H, W = w.shape
+    a = np.ascontiguousarray(accum, np.float32).reshape(H, W, 4)
+    flags = np.empty((H, W), np.uint8)
+    lib = oracle_lib()
+    lib.yc_aa_next_pass.restype = C.c_int
+    n = lib.yc_aa_next_pass(_p(a, C.c_float), _p(w, C.c_float), C.c_int(W), C.c_int(H), C.c_int(int(bool(detect_color_noise))),
+                            C.c_int(dark_type), C.c_float(dark_factor), C.c_int(variance_edge), C.c_int(variance_pixels),
+                            C.c_float(threshold), _p(flags, C.c_uint8))
+    assert n == int(flags.sum())
+    return flags
+
+
+def visiting_order(flags, tile, ry0=0, ry1=None):
+    """The flagged pixels (y * W + x) of rows [ry0, ry1) in the order the next pass visits them: linear tiles
+    (imagesplitter.cc:30-49), rows inside a tile (integrator_tiled.cc:269-290)."""
+    H, W = flags.shape
+    ry1 = H if ry1 is None else ry1
+    out = []
+    for tx, ty, tw, th in oracle_prims().tiles(W, H, tile, "linear"):
+        for y in range(max(ty, ry0), min(ty + th, ry1)):
+            row = np.nonzero(flags[y, tx:tx + tw])[0]
+            out.extend((y * W + tx + row).tolist())
+    return np.asarray(out, np.uint32)
 
 
 # ---- scene-level oracle ------------------------------------------------------------------------

@@ -296,6 +296,33 @@ void ref_rgbe_decode(const uint8_t *rgbe, float *rgb, int n)
 	}
 }
 
+// The colour arithmetic under ImageFilm::nextPass (color.h): ab = two RGBA colours per element (this, color_2)
+void ref_color_difference(const float *ab, int use_rgb, float *out, int n)
+{
+	for(int i = 0; i < n; ++i)
+	{
+		const float *p = ab + 8 * i;
+		const Rgba a{p[0], p[1], p[2], p[3]}, b{p[4], p[5], p[6], p[7]};
+		out[i] = a.colorDifference(b, use_rgb != 0);
+	}
+}
+
+// Rgba::normalized: cw = RGBA + weight per element
+void ref_normalized(const float *cw, float *out, int n)
+{
+	for(int i = 0; i < n; ++i)
+	{
+		const float *p = cw + 5 * i;
+		const Rgba r = Rgba{p[0], p[1], p[2], p[3]}.normalized(p[4]);
+		out[4 * i] = r.r_; out[4 * i + 1] = r.g_; out[4 * i + 2] = r.b_; out[4 * i + 3] = r.a_;
+	}
+}
+
+void ref_abscol2bri(const float *rgb, float *out, int n)
+{
+	for(int i = 0; i < n; ++i) out[i] = Rgb{rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]}.abscol2Bri();
+}
+
 // ImageSplitter (imagesplitter.cc:30-107): the region list of an image, order 0 linear, 1 random,
 // 2 centre (TilesOrderType), for `nthreads` render threads; out = (x, y, w, h) per region, returns
 // the region count (<= cap)

@@ -3206,13 +3206,23 @@ static float darkThresholdCurve(float b)
 struct Rgba4 { float r, g, b, a; };
 
 // Rgba::normalized (color.h:554-558, operator/ :312-316)
-static Rgba4 filmColor(const Film &film, int W, int x, int y)
+static Rgba4 normalized(const float *c, float w)
 {
-	const size_t p = (size_t)y * W + x;
-	const float w = film.weight[p];
 	if(w == 0.f) return {0.f, 0.f, 0.f, 0.f};
 	const float f = 1.f / w;
-	return {film.rgba[4 * p] * f, film.rgba[4 * p + 1] * f, film.rgba[4 * p + 2] * f, film.rgba[4 * p + 3] * f};
+	return {c[0] * f, c[1] * f, c[2] * f, c[3] * f};
+}
+
+// Rgb::abscol2Bri (color.h:62)
+static float abscol2Bri(const Rgba4 &c) { return 0.2126f * std::abs(c.r) + 0.7152f * std::abs(c.g) + 0.0722f * std::abs(c.b); }
+
+// the accumulated film nextPass reads: the render's Film or caller-supplied arrays (yc_aa_next_pass)
+struct FilmView { const float *rgba, *weight; };
+
+static Rgba4 filmColor(const FilmView &film, int W, int x, int y)
+{
+	const size_t p = (size_t)y * W + x;
+	return normalized(film.rgba + 4 * p, film.weight[p]);
 }
 
 // Rgba::colorDifference (color.h:450-467), col2Bri (color.h:61)
@@ -3235,7 +3245,7 @@ static float colorDifference(const Rgba4 &a, const Rgba4 &c2, bool rgb)
 // ImageFilm::nextPass (imagefilm.cc:259-420) with adaptive_aa = true and no DebugSamplingFactor
 // layer: flags the pixels the next pass resamples; returns their count.  doMoreSamples
 // (:672-675) resamples every pixel when the threshold is <= 0.
-static int aaNextPass(const Film &film, int W, int H, const yc_render &rp, float threshold, std::vector<uint8_t> &flags)
+static int aaNextPass(const FilmView &film, int W, int H, const yc_render &rp, float threshold, std::vector<uint8_t> &flags)
 {
 	flags.assign((size_t)W * H, 0);
 	if(!(threshold > 0.f))
@@ -3253,7 +3263,7 @@ static int aaNextPass(const Film &film, int W, int H, const yc_render &rp, float
 		for(int x = 0; x < W - 1; ++x)
 		{
 			const Rgba4 pc = filmColor(film, W, x, y);
-			const float bri = 0.2126f * std::abs(pc.r) + 0.7152f * std::abs(pc.g) + 0.0722f * std::abs(pc.b);   // abscol2Bri
+			const float bri = abscol2Bri(pc);
 			if(rp.aa_dark_detection_type == 1 && rp.aa_dark_threshold_factor > 0.f)
 				th = threshold * ((1.f - rp.aa_dark_threshold_factor) + (bri * rp.aa_dark_threshold_factor));
 			else if(rp.aa_dark_detection_type == 2) th = darkThresholdCurve(bri);
@@ -3396,7 +3406,7 @@ static int renderImage(const yc_scene *s, int y0, int y1, float *out_rgba, float
 		if(resampled <= 0.f && !threshold_changed) {}   // nextPass(..., skipNextPass = true): flags untouched
 		else
 		{
-			resampled = aaNextPass(film, W, H, rp, threshold, flags);
+			resampled = aaNextPass(FilmView{film.rgba.data(), film.weight.data()}, W, H, rp, threshold, flags);
 			threshold_changed = false;
 			if(const char *dump = getenv("YC_AA_DUMP"); dump && *dump)
 				if(FILE *f = fopen((std::string(dump) + "_pass" + std::to_string(pass) + ".bin").c_str(), "wb"))
@@ -3681,6 +3691,62 @@ void yc_mwc(uint32_t seed, int steps, double *out)
 void yc_filter_gauss(const float *dxdy, float *out, int n) { for(int i = 0; i < n; ++i) out[i] = filterGauss(dxdy[2 * i], dxdy[2 * i + 1]); }
 void yc_filter_mitchell(const float *dxdy, float *out, int n) { for(int i = 0; i < n; ++i) out[i] = filterMitchell(dxdy[2 * i], dxdy[2 * i + 1]); }
 void yc_filter_lanczos(const float *dxdy, float *out, int n) { for(int i = 0; i < n; ++i) out[i] = filterLanczos(dxdy[2 * i], dxdy[2 * i + 1]); }
+// the colour arithmetic under nextPass, pinned against oracle/_ref ref_color_difference / ref_normalized /
+// ref_abscol2bri (color.h:450-467, 554-558, 62); ab: two RGBA colours per element, cw: RGBA + weight
+void yc_color_difference(const float *ab, int use_rgb, float *out, int n)
+{
+	for(int i = 0; i < n; ++i)
+	{
+		const float *p = ab + 8 * i;
+		out[i] = colorDifference(Rgba4{p[0], p[1], p[2], p[3]}, Rgba4{p[4], p[5], p[6], p[7]}, use_rgb != 0);
+	}
+}
+void yc_normalized(const float *cw, float *out, int n)
+{
+	for(int i = 0; i < n; ++i)
+	{
+		const Rgba4 c = normalized(cw + 5 * i, cw[5 * i + 4]);
+		out[4 * i] = c.r; out[4 * i + 1] = c.g; out[4 * i + 2] = c.b; out[4 * i + 3] = c.a;
+	}
+}
+void yc_abscol2bri(const float *rgb, float *out, int n)
+{
+	for(int i = 0; i < n; ++i) out[i] = abscol2Bri(Rgba4{rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.f});
+}
+void yc_dark_threshold_curve(const float *b, float *out, int n) { for(int i = 0; i < n; ++i) out[i] = darkThresholdCurve(b[i]); }
+
+// ImageFilm::nextPass's flags for a caller-supplied accumulated film (the body the adaptive render runs);
+// returns the number of flagged pixels
+int yc_aa_next_pass(const float *accum, const float *weights, int W, int H, int detect_color_noise, int dark_type, float dark_factor,
+                    int variance_edge, int variance_pixels, float threshold, uint8_t *flags)
+{
+	yc_render rp{};
+	rp.aa_detect_color_noise = detect_color_noise;
+	rp.aa_dark_detection_type = dark_type;
+	rp.aa_dark_threshold_factor = dark_factor;
+	rp.aa_variance_edge_size = variance_edge;
+	rp.aa_variance_pixels = variance_pixels;
+	std::vector<uint8_t> f;
+	const int n = aaNextPass(FilmView{accum, weights}, W, H, rp, threshold, f);
+	std::memcpy(flags, f.data(), f.size());
+	return n;
+}
+
+// final gathering's radiance-point thinning on caller-supplied points (the body buildRadianceMap runs): pos / nrm
+// n x 3 floats; kept: n entries of capacity; returns the kept count
+int yc_thin_rad_points(const float *pos, const float *nrm, int n, float maxrad, uint32_t *kept)
+{
+	std::vector<Renderer::RadData> pts((size_t)n);
+	for(int i = 0; i < n; ++i)
+	{
+		pts[i].pos = V3(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]);
+		pts[i].normal = V3(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]);
+	}
+	const std::vector<uint32_t> k = Renderer::eliminateRadPoints(pts, maxrad);
+	std::copy(k.begin(), k.end(), kept);
+	return (int)k.size();
+}
+
 void yc_round_to_int(const double *v, int *out, int n) { for(int i = 0; i < n; ++i) out[i] = roundToInt(v[i]); }
 void yc_floor_to_int(const double *v, int *out, int n) { for(int i = 0; i < n; ++i) out[i] = floorToInt(v[i]); }
 void yc_clamp_proportional(const float *rgb, float max_value, float *out, int n)

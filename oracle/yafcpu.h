@@ -265,5 +265,16 @@ void yc_round_to_int(const double *v, int *out, int n);
 void yc_floor_to_int(const double *v, int *out, int n);
 void yc_clamp_proportional(const float *rgb, float max_value, float *out, int n);
 void yc_film_table(int filter, float filter_size, float *table16x16, float *filterw, float *table_scale);
+void yc_color_difference(const float *ab, int use_rgb, float *out, int n);
+void yc_normalized(const float *cw, float *out, int n);
+void yc_abscol2bri(const float *rgb, float *out, int n);
+void yc_dark_threshold_curve(const float *b, float *out, int n);
+
+// The two selection passes on caller-supplied data, each the body the render path runs.
+// nextPass (imagefilm.cc:259-420): flags (W * H bytes) of an accumulated film; returns how many are set.
+int yc_aa_next_pass(const float *accum, const float *weights, int W, int H, int detect_color_noise, int dark_type, float dark_factor,
+                    int variance_edge, int variance_pixels, float threshold, uint8_t *flags);
+// the radiance-point thinning (integrator_photon_mapping.cc:560-572): the kept indices, ascending; returns their count
+int yc_thin_rad_points(const float *pos, const float *nrm, int n, float maxrad, uint32_t *kept);
 
 }

@@ -10,6 +10,9 @@ The CPU oracle and the device numerics are pinned against this file (tests/test_
     python tests/golden/make_golden_prims.py filters
 writes only tests/golden/prims_filters.npz: the reference's mitchell and lanczos2 film filter functions, against
 which the oracle's and the product's host restatements are pinned (tests/test_oracle_golden.py).
+    python tests/golden/make_golden_prims.py aa
+writes only tests/golden/prims_aa.npz: the reference's Rgba::colorDifference (both settings of its flag),
+Rgba::normalized and Rgb::abscol2Bri, the colour arithmetic under ImageFilm::nextPass.
 """
 import os
 import sys
@@ -169,6 +172,49 @@ def main_filters():
     print("wrote", OUT_FILTERS, os.path.getsize(OUT_FILTERS), "bytes,", len(g), "arrays")
 
 
+# ---- the colour arithmetic under ImageFilm::nextPass (include/color/color.h colorDifference, normalized,
+# abscol2Bri): tests/golden/prims_aa.npz ----
+OUT_AA = os.path.join(os.path.dirname(OUT), "prims_aa.npz")
+
+
+def aa_inputs():
+    """(colour pairs (n, 8), colour + weight rows (n, 5), rgb (n, 3)): random signed colours, colours on a 1/8 lattice
+    (exact differences), and the special values: negative components, zero / negative / subnormal weights,
+    inf and NaN."""
+    rng = np.random.default_rng(0x6161)
+    n = 1024
+    f32 = np.float32
+    sub = f32(1e-41)                                    # subnormal
+    special = np.array([0.0, -0.0, 1.0, -1.0, 0.125, -0.125, sub, -sub, np.finfo(f32).tiny, np.finfo(f32).max,
+                        -np.finfo(f32).max, np.inf, -np.inf, np.nan], f32)
+    pairs = np.concatenate([rng.normal(0, 1, (n, 8)), rng.integers(-8, 17, (n, 8)) / 8.0]).astype(f32)
+    sp = special[rng.integers(0, len(special), (512, 8))]
+    mixed = rng.normal(0, 1, (512, 8)).astype(f32)
+    hole = rng.random((512, 8)) < 0.2
+    mixed[hole] = special[rng.integers(0, len(special), int(hole.sum()))]
+    pairs = np.concatenate([pairs, sp, mixed]).astype(f32)
+    cw = np.concatenate([rng.normal(0, 1, (n, 5)), rng.integers(-8, 17, (n, 5)) / 8.0]).astype(f32)
+    cw_sp = rng.normal(0, 1, (len(special) * 8, 5)).astype(f32)
+    cw_sp[:, 4] = np.repeat(special, 8)                 # every special weight, zero, negative and subnormal included
+    cw_sp[::4, :4] = special[rng.integers(0, len(special), (len(cw_sp[::4]), 4))]
+    cw = np.concatenate([cw, cw_sp]).astype(f32)
+    rgb = np.concatenate([rng.normal(0, 1, (n, 3)), rng.integers(-8, 17, (n, 3)) / 8.0,
+                          special[rng.integers(0, len(special), (256, 3))]]).astype(f32)
+    return pairs, cw, rgb
+
+
+def main_aa():
+    r = O.ref_prims()
+    if r is None or not r.has("color_difference"):
+        sys.exit("oracle/_ref not built with ref_color_difference (needs the reference tree): the committed prims_aa.npz is used as is")
+    pairs, cw, rgb = aa_inputs()
+    g = {"pairs": pairs, "cw": cw, "rgb": rgb,
+         "color_difference_bri": r.color_difference(pairs, False), "color_difference_rgb": r.color_difference(pairs, True),
+         "normalized": r.normalized(cw), "abscol2bri": r.abscol2bri(rgb)}
+    np.savez_compressed(OUT_AA, **g)
+    print("wrote", OUT_AA, os.path.getsize(OUT_AA), "bytes,", len(g), "arrays")
+
+
 if __name__ == "__main__":
-    # "filters": only prims_filters.npz (prims.npz and prims_r02.npz stay as committed)
-    main_filters() if sys.argv[1:] == ["filters"] else main()
+    # "filters" / "aa": only prims_filters.npz / prims_aa.npz (prims.npz and prims_r02.npz stay as committed)
+    {("filters",): main_filters, ("aa",): main_aa}.get(tuple(sys.argv[1:]), main)()

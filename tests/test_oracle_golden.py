@@ -187,6 +187,85 @@ def test_live_reference_film_filters_random_inputs(o, oracle_built):
         assert same(o.film_filter(name, d), r.film_filter(name, d)), name
 
 
+# ---- the colour arithmetic under ImageFilm::nextPass (tests/golden/prims_aa.npz: color.h colorDifference with and
+# without the r, g, b, a components, normalized, abscol2Bri; negative, zero and subnormal weights, negative
+# components, inf and NaN among the inputs) ----
+GA = np.load(os.path.join(HERE, "golden", "prims_aa.npz"))
+
+
+def test_aa_fixture_covers_the_special_values():
+    w = GA["cw"][:, 4]
+    tiny = np.finfo(np.float32).tiny
+    assert (w == 0).any() and (w < 0).any() and ((np.abs(w) > 0) & (np.abs(w) < tiny)).any()
+    for a in (GA["pairs"], GA["cw"][:, :4], GA["rgb"]):
+        assert (a < 0).any() and np.isinf(a).any() and np.isnan(a).any()
+    # a zero weight gives the zero colour, a negative one divides (color.h:554-558)
+    assert (GA["normalized"][w == 0] == 0).all()
+    neg = (w < -1e-3) & (w > -1e3) & (np.abs(GA["cw"][:, 0]) > 1e-3) & (np.abs(GA["cw"][:, 0]) < 1e3)
+    assert neg.any() and (np.sign(GA["normalized"][neg, 0]) == -np.sign(GA["cw"][neg, 0])).all()
+    # the r, g, b, a components only ever raise the difference, and alpha alone can
+    assert (GA["color_difference_rgb"] > GA["color_difference_bri"]).any()
+
+
+def test_aa_colour_arithmetic(o):
+    assert same(o.color_difference(GA["pairs"], False), GA["color_difference_bri"])
+    assert same(o.color_difference(GA["pairs"], True), GA["color_difference_rgb"])
+    assert same(o.normalized(GA["cw"]), GA["normalized"])
+    assert same(o.abscol2bri(GA["rgb"]), GA["abscol2bri"])
+
+
+def test_live_reference_aa_colour_arithmetic_random_inputs(o, oracle_built):
+    r = oracle_built.ref_prims()
+    if r is None:
+        pytest.skip("oracle/_ref not built (reference tree absent): golden vectors above still pin the oracle")
+    if not (r.has("color_difference") and r.has("normalized") and r.has("abscol2bri")):
+        pytest.skip("oracle/_ref predates ref_color_difference / ref_normalized / ref_abscol2bri and was not rebuilt "
+                    "(reference tree absent): golden vectors above still pin the oracle")
+    rng = np.random.default_rng(777)
+    pairs = np.concatenate([rng.normal(0, 2, (100000, 8)), rng.integers(-16, 33, (20000, 8)) / 8.0]).astype(np.float32)
+    cw = rng.normal(0, 2, (100000, 5)).astype(np.float32)
+    cw[::7, 4] = 0
+    for flag in (False, True):
+        assert same(o.color_difference(pairs, flag), r.color_difference(pairs, flag)), flag
+    assert same(o.normalized(cw), r.normalized(cw))
+    assert same(o.abscol2bri(pairs[:, :3]), r.abscol2bri(pairs[:, :3]))
+
+
+# the table of ImageFilm::darkThresholdCurveInterpolate (imagefilm.cc:799-815, not linkable on its own): segment
+# ends (brightness, threshold); constant below the first and above the last
+DARK_CURVE = [(0.10, 0.0001), (0.20, 0.0010), (0.30, 0.0020), (0.40, 0.0035), (0.50, 0.0055), (0.60, 0.0075), (0.70, 0.0100),
+              (0.80, 0.0150), (0.90, 0.0250), (1.00, 0.0400), (1.20, 0.0800), (1.40, 0.0950), (1.80, 0.1000)]
+
+
+def dark_curve_table(b):
+    """The curve from the table, in the reference's float32 expression order: lo + (b - b_lo) * (hi - lo) / (b_hi - b_lo)."""
+    f = np.float32
+    b = f(b)
+    if b <= f(DARK_CURVE[0][0]):
+        return f(DARK_CURVE[0][1])
+    for (b0, t0), (b1, t1) in zip(DARK_CURVE[:-1], DARK_CURVE[1:]):
+        if b <= f(b1):
+            width = f(round(b1 - b0, 2))     # the reference writes the segment widths as the literals 0.10f, 0.20f, 0.40f
+            return f(f(t0) + f(f(f(b - f(b0)) * f(f(t1) - f(t0))) / width))
+    return f(DARK_CURVE[-1][1])
+
+
+def test_dark_threshold_curve_table(oracle_built):
+    """The oracle's curve at, just below and just above each breakpoint (and at 0, far above and negative)."""
+    f = np.float32
+    pts = [f(0.0), f(-1.0), f(5.0), f(np.inf)]
+    for b, _ in DARK_CURVE:
+        pts += [np.nextafter(f(b), f(-np.inf)), f(b), np.nextafter(f(b), f(np.inf))]
+    pts += [f(0.15), f(0.55), f(1.1), f(1.6)]
+    pts = np.array(pts, f)
+    got = oracle_built.dark_threshold_curve(pts)
+    want = np.array([dark_curve_table(b) for b in pts], f)
+    assert same(got, want), [(float(b), float(g), float(w)) for b, g, w in zip(pts, got, want) if g != w]
+    # the curve is continuous to float rounding and never decreases
+    order = np.argsort(pts[np.isfinite(pts)])
+    assert (np.diff(got[np.isfinite(pts)][order]) >= -1e-9).all()
+
+
 # ---- texturing building blocks (tests/golden/tex_prims.npz, made by make_golden_tex.py from the
 # reference's own image_buffers.h / color.h / interpolation.h / math.h) ----
 TEX_KINDS = {0: "Rgba1010108", 1: "Rgb101010", 2: "Rgba7773", 3: "Rgb565", 4: "Gray8", 5: "Gray", 6: "GrayAlpha", 7: "RgbAlpha"}
