@@ -14,6 +14,7 @@
 #include <cstdint>
 
 #include "devscene.h"
+#include "launch.h"
 
 namespace
 {

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "bvh.h"
+#include "launch.h"
 
 namespace
 {

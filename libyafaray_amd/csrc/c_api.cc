@@ -7,6 +7,7 @@
 #include "texture.h"
 #include "hostmath.h"
 #include "render.h"
+#include "launch.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -29,8 +30,6 @@ static char *dupString(const std::string &s)
 	return c;
 }
 
-extern "C" int yafamd_phase_cycles(unsigned long long *out, int n, int reset);
-extern "C" const char *yafamd_device_build();
 #define YAF_HOST_BUILD "hipcc/clang " __VERSION__ " -O3 -ffp-contract=off"
 
 extern "C" {
@@ -776,8 +775,6 @@ int yafaray_amd_rebalanceBands(const int *bounds, int world, const double *times
 // the point kd-tree build on its own (a batched seam for PointKdTree<T>::PointKdTree,
 // include/photon/pkdtree.h:115-222): n positions (xyz) in, 2n - 1 nodes (4 x uint32 each, the
 // layout of pkd.hip) and the deepest level out; runs on the current HIP device with its own stream
-extern "C" hipError_t yafamd_build_pkd(const float4 *pos_dev, uint32_t n, uint4 *nodes_dev, int *depth_out, hipStream_t st, void **scratch);
-extern "C" void yafamd_pkd_scratch_free(void *scratch);
 yafaray_bool_t yafaray_amd_buildPhotonTree(const float *xyz, int n, unsigned int *nodes, int *depth)
 {
 	if(!xyz || !nodes || !depth || n < 1) return YAFARAY_BOOL_FALSE;
@@ -803,11 +800,6 @@ yafaray_bool_t yafaray_amd_buildPhotonTree(const float *xyz, int n, unsigned int
 // (1.6) a device / render group member's share of the distributed build (pkd.hip yafamd_build_pkd_kd_member):
 // the whole top above the split level and the member's own subtrees, nodes and kd-order positions out
 // (the other members' ranges zero); built twice, *ms = the second build's device time
-extern "C" hipError_t yafamd_build_pkd_kd_member(const float4 *pos_dev, const float4 *dir_dev, const float *colb_dev, uint32_t n, uint4 *nodes_dev,
-                                                 float4 *kpos, float4 *kdir, float *kcolb, int *depth_out, hipStream_t st, void **scratch, int member,
-                                                 int members, int *split_level);
-extern "C" void yafamd_pkd_top_segments(uint32_t n, int level, uint32_t *out);
-extern "C" void yafamd_pkd_owned_segments(int level, int member, int members, uint32_t *s0, uint32_t *s1);
 yafaray_bool_t yafaray_amd_buildPhotonTreeMember(const float *xyz, int n, int member, int members, unsigned int *nodes, float *kd_pos, int *depth,
                                                  int *split_level, double *ms)
 {

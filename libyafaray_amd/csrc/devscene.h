@@ -389,7 +389,7 @@ struct DevFilm
 	int crop_x0, crop_y0;          // cropped film: the sample positions hash the camera pixel (x + crop_x0, y + crop_y0)
 };
 
-// ---- render layers (layers_kernels.h): the first-hit layers of a render that defines any ----
+// ---- render layers (layers.hip): the first-hit layers of a render that defines any ----
 // The kinds in the reference's LayerDef::Type order (the order of the film's layer planes, of the
 // callbacks and of the film file).
 enum : int

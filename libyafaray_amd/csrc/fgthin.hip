@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "devscene.h"
+#include "launch.h"
 
 namespace
 {

@@ -23,6 +23,7 @@
 
 #include "devmath.h"
 #include "devscene.h"
+#include "launch.h"
 
 namespace
 {

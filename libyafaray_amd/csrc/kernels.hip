@@ -2,7 +2,7 @@
 //
 // Wavefront pipeline for one chunk of camera samples (render.cc drives it):
 //
-//   k_camera  -> [ k_trace -> k_shade ] x iterations -> (all chunks) -> k_film
+//   k_camera  -> [ k_trace -> k_shade ] x iterations -> (all chunks) -> k_film (film.hip)
 //
 //   k_camera : one camera sample per slot — TiledIntegrator::renderTile sample loop
 //              (integrator_tiled.cc:288-361) + PerspectiveCamera::shootRay
@@ -19,10 +19,10 @@
 //              the next extension ray / shadow rays with wave-ballot compaction
 //              (PathIntegrator::integrate integrator_path_tracer.cc:120-290,
 //               DirectLightIntegrator::integrate integrator_direct_light.cc:97-144).
-//   k_film   : ImageFilm::addSample (imagefilm.cc:680-733) as a per-destination-pixel gather
-//              that replays the reference's single-thread linear-tile splat order, so every film
-//              sum is bit-identical without a mutex or atomics; then flush normalisation
-//              (imagefilm.cc:590-617, color.h:554-558).
+//
+// Photon shooting, the photon gather and final gathering follow the path tracer below.  The film kernels and the
+// render layers are units of their own (film.hip, layers.hip); the sample coordinates and camera rays they share
+// with k_camera and k_shade are in camera.h.
 //
 // Compiled with -ffp-contract=off: every float expression keeps the reference's order.
 
@@ -35,6 +35,8 @@
 #include "devscene.h"
 #include "trace.h"
 #include "texeval.h"
+#include "camera.h"
+#include "launch.h"
 
 namespace yafamd
 {
@@ -300,162 +302,8 @@ __device__ unsigned long long g_phase[16];
 #endif
 
 // ---------------------------------------------------------------------------------------------
-// k_camera
+// k_camera (sampleAt, cameraRay: camera.h)
 // ---------------------------------------------------------------------------------------------
-struct SampleCoord { int x, y, s; };
-
-// sample id (frame-local enumeration over jobs) -> pixel + sample index
-__device__ SampleCoord sampleCoord(const DevJob *jobs, int n_jobs, int width, int tile, int spp, uint64_t sid)
-{
-	// last job whose first sample is <= sid (jobs are in ascending sample_base order)
-	int j = 0, hi = n_jobs - 1;
-	while(j < hi)
-	{
-		const int mid = (j + hi + 1) >> 1;
-		if(jobs[mid].sample_base <= sid) j = mid;
-		else hi = mid - 1;
-	}
-	const DevJob job = jobs[j];
-	const uint64_t local = sid - job.sample_base;
-	const uint32_t pix = (uint32_t)(local / (uint64_t)spp);
-	const int s = (int)(local % (uint64_t)spp);
-	const int bh = job.y1 - job.y0;
-	const uint32_t per_tile = (uint32_t)(tile * bh);
-	const int tx = (int)(pix / per_tile);
-	const int tw = min(tile, width - tx * tile);
-	const uint32_t l = pix - (uint32_t)tx * per_tile;
-	SampleCoord c;
-	c.x = tx * tile + (int)(l % (uint32_t)tw);
-	c.y = job.y0 + (int)(l / (uint32_t)tw);
-	c.s = s;
-	return c;
-}
-
-// camera_perspective.cc:71-85
-__device__ __forceinline__ float biasDist(int bias, float r)
-{
-	if(bias == 1) return sqrtf(sqrtf(r) * r);           // BbCenter
-	if(bias == 2) return sqrtf(1.f - r * r);            // BbEdge
-	return sqrtf(r);                                    // BbNone
-}
-
-// vector.cc:128-163 (the long double pi/4 products round like x87)
-__device__ __forceinline__ void shirleyDisk(float r_1, float r_2, float &u, float &v)
-{
-	float phi = 0.f, r = 0.f;
-	const float a = 2.f * r_1 - 1.f, b = 2.f * r_2 - 1.f;
-	if(a > -b)
-	{
-		if(a > b) { r = a; phi = x87mul(kDivPiBy4, b / a); }
-		else { r = b; phi = x87mul(kDivPiBy4, 2.f - a / b); }
-	}
-	else
-	{
-		if(a < b) { r = -a; phi = x87mul(kDivPiBy4, 4.f + b / a); }
-		else
-		{
-			r = -b;
-			phi = (b != 0) ? x87mul(kDivPiBy4, 6.f - a / b) : 0.f;
-		}
-	}
-	u = r * fcos(phi);
-	v = r * fsin(phi);
-}
-
-// camera_perspective.cc:87-124 getLensUv (sampleTsd for the polygon bokehs)
-__device__ void lensUv(const DevCamera &c, float r_1, float r_2, float &u, float &v)
-{
-	const int t = c.bokeh_type;
-	if(t >= 3 && t <= 6)
-	{
-		const float fn = static_cast<float>(t);
-		int idx = int(r_1 * fn);
-		r_1 = (r_1 - ((float)idx) / fn) * fn;
-		r_1 = biasDist(c.bokeh_bias, r_1);
-		const float b_1 = r_1 * r_2;
-		const float b_0 = r_1 - b_1;
-		idx <<= 1;
-		u = c.ls[idx] * b_0 + c.ls[idx + 2] * b_1;
-		v = c.ls[idx + 1] * b_0 + c.ls[idx + 3] * b_1;
-	}
-	else if(t == 1 || t == 7)
-	{
-		const float w = 6.28318548f * r_2;   // (float)math::mult_pi_by_2 * r_2
-		if(t == 7) r_1 = sqrtf((float)0.707106781 + (float)0.292893218);
-		else r_1 = biasDist(c.bokeh_bias, r_1);
-		u = r_1 * fcos(w);
-		v = r_1 * fsin(w);
-	}
-	else shirleyDisk(r_1, r_2, u, v);
-}
-
-// sample id -> pixel + sample index: the jobs' enumeration, or an adaptive pass's pixel list
-__device__ __forceinline__ SampleCoord sampleAt(const DevScene &S, const DevJob *jobs, int n_jobs, uint64_t sid)
-{
-	if(S.plist)
-	{
-		const uint32_t pix = S.plist[sid / (uint64_t)S.spp];
-		SampleCoord c;
-		c.x = (int)(pix % (uint32_t)S.width);
-		c.y = (int)(pix / (uint32_t)S.width);
-		c.s = (int)(sid % (uint64_t)S.spp);
-		return c;
-	}
-	return sampleCoord(jobs, n_jobs, S.width, S.tile, S.spp, sid);
-}
-
-// One camera sample: TiledIntegrator::renderTile's sample position (integrator_tiled.cc:313-340) and
-// PerspectiveCamera::shootRay (camera_perspective.cc:128-146), plus the sample's Russian-roulette seed.
-// k_camera (wavefront) and k_path (megakernel) both start their samples here.
-__device__ __forceinline__ void cameraRay(const DevScene &S, const SampleCoord &sc, V3 &from, V3 &dir, float &tmin, float &tmax, uint32_t &seed)
-{
-	// integrator_tiled.cc:313-335 (camera pixel coordinates: a cropped film starts at crop_x0 / crop_y0)
-	const int cx = sc.x + S.crop_x0, cy = sc.y + S.crop_y0;
-	const uint32_t offset = fnv32((uint32_t)cy * fnv32((uint32_t)cx));
-	const uint32_t sample_idx = S.base_offset + S.pass_offset + (uint32_t)sc.s;   // PixelSamplingData::sample_
-	float dx = 0.5f, dy = 0.5f;
-	if(S.aa_multipass)
-	{
-		dx = riVdC(sample_idx, offset);
-		dy = riS(sample_idx, offset);
-	}
-	else if(S.spp > 1)
-	{
-		const float d_1 = 1.f / (float)S.spp;
-		dx = (0.5f + (float)sc.s) * d_1;
-		dy = riLp((uint32_t)sc.s + offset);
-	}
-	const float px = (float)cx + dx, py = (float)cy + dy;
-	// camera_perspective.cc:128-146, plane.h:37-40
-	const DevCamera &c = S.cam;
-	const V3 pos = v3(c.pos[0], c.pos[1], c.pos[2]);
-	dir = v3(c.vright[0], c.vright[1], c.vright[2]) * px + v3(c.vup[0], c.vup[1], c.vup[2]) * py + v3(c.vto[0], c.vto[1], c.vto[2]);
-	dir = normalize(dir);
-	const V3 cz = v3(c.cam_z[0], c.cam_z[1], c.cam_z[2]);
-	tmin = dot(cz, v3(c.near_p[0], c.near_p[1], c.near_p[2]) - pos) / dot(dir, cz);
-	tmax = dot(cz, v3(c.far_p[0], c.far_p[1], c.far_p[2]) - pos) / dot(dir, cz);
-	from = pos;
-	if(c.aperture != 0.f)
-	{
-		// integrator_tiled.cc:314-316, 336-340: Halton(3) / Halton(5) lens streams started at the
-		// pass offset + pixel offset, one getNext() per sample; camera_perspective.cc:137-144
-		const uint32_t hstart = S.base_offset + S.pass_offset + offset;
-		const float lu = haltonNext(3u, hstart, sc.s + 1), lv = haltonNext(5u, hstart, sc.s + 1);
-		float u, v;
-		lensUv(c, lu, lv, u, v);
-		const V3 li = v3(c.dof_rt[0], c.dof_rt[1], c.dof_rt[2]) * u + v3(c.dof_up[0], c.dof_up[1], c.dof_up[2]) * v;
-		from = from + li;
-		dir = normalize(dir * c.dof_distance - li);
-	}
-	// RR generator: per-sample MWC (the reference seeds one per tile from rand(), so RR
-	// output is matched statistically — integrator_tiled.cc:272), seeded from the pixel-major sample
-	// id so that the image does not depend on how the film is split over GPUs or chunks
-	// (64-bit id: W * H * spp passes 2^32 at 4K x 1024 spp; both halves are hashed)
-	const uint64_t gid = ((uint64_t)sc.y * (uint64_t)S.width + (uint64_t)sc.x) * (uint64_t)S.spp + (uint64_t)sc.s;
-	const uint32_t gid32 = (uint32_t)gid ^ fnv32((uint32_t)(gid >> 32));
-	seed = fnv32(gid32 ^ S.rr_seed ^ (S.pass_offset * 0x9e3779b9u)) + 123u;
-}
-
 __global__ void __launch_bounds__(256) k_camera(DevScene S, DevPaths P, DevQueues Q, DevCounters cnt,
                                                  const DevJob *jobs, int n_jobs, uint64_t chunk_base, int n, int write_pr)
 {
@@ -3755,195 +3603,6 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_film: deterministic gather splat + flush normalisation
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int roundToInt(double v) { return (int)(v + (.5 - 1.4e-11)); }
-__device__ __forceinline__ int floorToInt(double v) { return (int)floor(v); }
-
-// rank of a pixel in the single-thread tile order (imagesplitter.cc:30-107): tiles by their rank
-// (linear when F.tile_rank is null), pixels row-major inside a tile (integrator_tiled.cc:288-290)
-__device__ __forceinline__ uint32_t tileRankOf(const DevFilm &F, int x, int y)
-{
-	const int ty = y / F.tile, tx = x / F.tile;
-	return F.tile_rank ? F.tile_rank[ty * F.ntx + tx] : (uint32_t)(ty * F.ntx + tx);
-}
-__device__ __forceinline__ uint64_t pixelRank(const DevFilm &F, int x, int y, int W, int H, int ts)
-{
-	const int ty = y / ts, tx = x / ts;
-	const int tw = min(ts, W - tx * ts);
-	return (uint64_t)tileRankOf(F, x, y) * (uint64_t)ts * ts + (uint64_t)(y - ty * ts) * tw + (x - tx * ts);
-}
-
-// RF / RB: compile-time footprint reach (box and gauss filters: RF = 1, RB = 0 -> a 2x2 window
-// kept in registers); RF = RB = -1 selects the generic runtime window (<= 9x9).
-template<int RF, int RB>
-__global__ void __launch_bounds__(256) k_film(DevFilm F, const float4 *samples, const uint8_t *flags, float4 *accum,
-                                              float4 *out, float *weights, int y0, int y1, float clamp_samples, int accumulate)
-{
-	constexpr bool kStatic = RF >= 0;
-	constexpr int kWin = kStatic ? (RF + RB + 1) * (RF + RB + 1) : 81;
-	const int x = blockIdx.x * blockDim.x + threadIdx.x;
-	const int y = y0 + blockIdx.y;
-	if(x >= F.width || y >= y1) return;
-	const int W = F.width, H = F.height, spp = F.spp;
-	const int rf = kStatic ? RF : F.reach_fwd, rb = kStatic ? RB : F.reach_back;
-	// candidate sources, sorted by their rank in the reference's splat order
-	int sx[kWin], sy[kWin];
-	uint64_t rk[kWin];
-	int n = 0;
-	const uint32_t own_tile = F.partial ? tileRankOf(F, x, y) : 0u;
-#pragma unroll
-	for(int dyy = 0; dyy < (kStatic ? RF + RB + 1 : 9); ++dyy)
-	{
-#pragma unroll
-		for(int dxx = 0; dxx < (kStatic ? RF + RB + 1 : 9); ++dxx)
-		{
-			if(!kStatic && (dyy > rf + rb || dxx > rf + rb)) continue;
-			const int yy = y - rf + dyy, xx = x - rf + dxx;
-			if(yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
-			if(F.partial && tileRankOf(F, xx, yy) > own_tile) continue;   // tile not finished yet
-			const uint64_t r = pixelRank(F, xx, yy, W, H, F.tile);
-			int p = n++;
-			while(p > 0 && rk[p - 1] > r) { rk[p] = rk[p - 1]; sx[p] = sx[p - 1]; sy[p] = sy[p - 1]; --p; }
-			rk[p] = r; sx[p] = xx; sy[p] = yy;
-		}
-	}
-	const size_t p = (size_t)y * W + x;
-	// adaptive passes add to the film of the earlier passes (imagefilm.cc addSample: += per sample)
-	float wsum = accumulate ? weights[p] : 0.f;
-	float4 acc = accumulate ? accum[p] : make_float4(0.f, 0.f, 0.f, 0.f);
-	const float d_1 = 1.f / (float)spp;
-	for(int c = 0; c < n; ++c)
-	{
-		const int px = sx[c], py = sy[c];
-		const uint32_t offset = fnv32((uint32_t)(py + F.crop_y0) * fnv32((uint32_t)(px + F.crop_x0)));
-		const int ox = x - px, oy = y - py;
-		// adaptive pass: only resampled pixels splat.  (Skipping them while building the candidate list
-		// instead lost diagonal candidates in the unrolled k_film<1, 0> — tools/film_probe.hip.)
-		const int ns = (flags && !flags[(size_t)py * W + px]) ? 0 : spp;
-		for(int s = 0; s < ns; ++s)
-		{
-			float dx = 0.5f, dy = 0.5f;
-			if(F.multipass)
-			{
-				dx = riVdC(F.sample_offset + (uint32_t)s, offset);
-				dy = riS(F.sample_offset + (uint32_t)s, offset);
-			}
-			else if(spp > 1)
-			{
-				dx = (0.5f + (float)s) * d_1;
-				dy = riLp((uint32_t)s + offset);
-			}
-			// imagefilm.cc:684-707 footprint of this sample, then the table weight at (x, y)
-			const int dx_0 = max(0 - px, roundToInt((double)dx - F.filterw));
-			const int dx_1 = min(W - px - 1, roundToInt((double)dx + F.filterw - 1.0));
-			const int dy_0 = max(0 - py, roundToInt((double)dy - F.filterw));
-			const int dy_1 = min(H - py - 1, roundToInt((double)dy + F.filterw - 1.0));
-			if(ox < dx_0 || ox > dx_1 || oy < dy_0 || oy > dy_1) continue;
-			const int xi = floorToInt(fabs(((double)ox - (dx - 0.5)) * F.table_scale));
-			const int yi = floorToInt(fabs(((double)oy - (dy - 0.5)) * F.table_scale));
-			const float wt = F.table[yi * 16 + xi];
-			wsum = wsum + wt;
-			const float4 col = samples[((size_t)py * W + px) * spp + s];
-			float r = col.x, g = col.y, b = col.z;
-			if(clamp_samples > 0.f)
-			{
-				// color.h:415-440 clampProportionalRgb
-				const float max_rgb = fmaxf(r, fmaxf(g, b));
-				const float adj = clamp_samples / max_rgb;
-				if(max_rgb > clamp_samples)
-				{
-					if(r >= max_rgb) { r = clamp_samples; g *= adj; b *= adj; }
-					else if(g >= max_rgb) { g = clamp_samples; r *= adj; b *= adj; }
-					else { b = clamp_samples; r *= adj; g *= adj; }
-				}
-			}
-			acc.x = acc.x + r * wt;
-			acc.y = acc.y + g * wt;
-			acc.z = acc.z + b * wt;
-			acc.w = acc.w + col.w * wt;
-		}
-	}
-	if(!F.partial)
-	{
-		weights[p] = wsum;
-		accum[p] = acc;
-	}
-	// Rgba::normalized (color.h:554-558): colour * (1 / weight) — operator/ takes the reciprocal first
-	if(wsum != 0.f)
-	{
-		const float inv = 1.f / wsum;
-		out[p] = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
-	}
-	else out[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-// Canceled render (integrator_tiled.cc:292: a canceled worker stops before its next pixel, so a
-// pixel is either fully sampled or not at all): flags the pixels whose samples the completed
-// chunks rendered, for k_film's `flags` argument.  Pass 0 enumerates the jobs (pixel ranks
-// [0, n_pix)); an adaptive pass (plist) clears the flags of its pixels beyond `done_pix`.
-__global__ void __launch_bounds__(256) k_done_flags(DevScene S, const DevJob *jobs, int n_jobs, uint32_t n_pix, uint32_t done_pix,
-                                                    uint8_t *flags)
-{
-	const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-	if(p >= n_pix) return;
-	if(S.plist)
-	{
-		if(p >= done_pix) flags[S.plist[p]] = 0;
-		return;
-	}
-	const SampleCoord c = sampleCoord(jobs, n_jobs, S.width, S.tile, S.spp, (uint64_t)p * (uint64_t)S.spp);
-	flags[(size_t)c.y * S.width + c.x] = p < done_pix ? 1 : 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// light-pick counters (DevScene::lpc, render.cc lpcBases).  A row segment = one row of one tile: its
-// pixels' counters (spp each) are contiguous in the pixel-major layout, and the one-thread render
-// visits them in that order (renderTile, integrator_tiled.cc:281-345: rows, then pixels, then
-// samples).  k_lpc_seg sums each segment of rows [y0, y1); k_lpc_prefix turns each segment's
-// counts into the counter values its samples start from: the segment's base (the calls of every
-// sample visited before the segment, from the host) + the exclusive prefix sum inside it.
-// One wave per segment.
-// ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_lpc_seg(const uint32_t *lpc, int W, int spp, int ts, int y0, int y1, uint32_t *seg)
-{
-	const int ntx = (W + ts - 1) / ts;
-	const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) / 64u), lane = (int)(threadIdx.x & 63u);
-	if(wave >= (y1 - y0) * ntx) return;
-	const int y = y0 + wave / ntx, tx = wave % ntx;
-	const int x0 = tx * ts, x1 = min(W, x0 + ts);
-	const size_t b = ((size_t)y * W + x0) * spp, n = (size_t)(x1 - x0) * spp;
-	uint32_t acc = 0;
-	for(size_t k = lane; k < n; k += 64) acc += lpc[b + k];
-	for(int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-	if(lane == 0) seg[(size_t)y * ntx + tx] = acc;
-}
-
-__global__ void __launch_bounds__(256) k_lpc_prefix(uint32_t *lpc, int W, int spp, int ts, int y0, int y1, const uint32_t *segbase)
-{
-	const int ntx = (W + ts - 1) / ts;
-	const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) / 64u), lane = (int)(threadIdx.x & 63u);
-	if(wave >= (y1 - y0) * ntx) return;
-	const int y = y0 + wave / ntx, tx = wave % ntx;
-	const int x0 = tx * ts, x1 = min(W, x0 + ts);
-	const size_t b = ((size_t)y * W + x0) * spp, n = (size_t)(x1 - x0) * spp;
-	uint32_t carry = segbase[(size_t)y * ntx + tx];
-	for(size_t k0 = 0; k0 < n; k0 += 64)
-	{
-		const size_t k = k0 + (size_t)lane;
-		const uint32_t v = k < n ? lpc[b + k] : 0u;
-		uint32_t x = v;
-		for(int off = 1; off < 64; off <<= 1)
-		{
-			const uint32_t t = __shfl_up(x, off);
-			if(lane >= off) x += t;
-		}
-		if(k < n) lpc[b + k] = carry + (x - v);
-		carry += __shfl(x, 63);
-	}
-}
-
-// ---------------------------------------------------------------------------------------------
 // ray-level entry (batched Accelerator::intersect / isShadowed for parity tests and hosts)
 // ---------------------------------------------------------------------------------------------
 template<bool ANY, bool WIDE>
@@ -4013,7 +3672,6 @@ __device__ __forceinline__ V3 sphereDir(float s_1, float s_2)
 	}
 	return dir;
 }
-
 
 constexpr uint32_t kDeadPhoton = 0xffffffffu;   // a hole in the segmented alive list (k_photon_emit)
 
@@ -7016,43 +6674,6 @@ size_t yafamd_gather_lanes(const DevScene *S) { return (size_t)S->n_seg * (kWalk
 
 size_t yafamd_gather_lds_bytes(const DevScene *S) { return gatherTableBytes(*S, S->small_tables != 0) + gatherLdsBytes(*S); }
 
-hipError_t yafamd_launch_done_flags(const DevScene *S, const DevJob *jobs, int n_jobs, uint32_t n_pix, uint32_t done_pix, uint8_t *flags,
-                                    hipStream_t st)
-{
-	if(n_pix == 0) return hipSuccess;
-	hipLaunchKernelGGL(k_done_flags, dim3((n_pix + 255) / 256), dim3(256), 0, st, *S, jobs, n_jobs, n_pix, done_pix, flags);
-	return hipGetLastError();
-}
-
-hipError_t yafamd_lpc_seg(const uint32_t *lpc, int W, int spp, int ts, int y0, int y1, uint32_t *seg, hipStream_t st)
-{
-	const int n = (y1 - y0) * ((W + ts - 1) / ts);
-	if(n <= 0) return hipSuccess;
-	hipLaunchKernelGGL(k_lpc_seg, dim3((n + 3) / 4), dim3(256), 0, st, lpc, W, spp, ts, y0, y1, seg);
-	return hipGetLastError();
-}
-
-hipError_t yafamd_lpc_prefix(uint32_t *lpc, int W, int spp, int ts, int y0, int y1, const uint32_t *segbase, hipStream_t st)
-{
-	const int n = (y1 - y0) * ((W + ts - 1) / ts);
-	if(n <= 0) return hipSuccess;
-	hipLaunchKernelGGL(k_lpc_prefix, dim3((n + 3) / 4), dim3(256), 0, st, lpc, W, spp, ts, y0, y1, segbase);
-	return hipGetLastError();
-}
-
-hipError_t yafamd_launch_film(const DevFilm *F, const float4 *samples, const uint8_t *flags, float4 *accum, float4 *out,
-                              float *weights, int y0, int y1, float clamp_samples, int accumulate, hipStream_t st)
-{
-	if(y1 <= y0) return hipSuccess;
-	const dim3 grid((F->width + 255) / 256, y1 - y0);
-	if(F->reach_fwd == 1 && F->reach_back == 0)
-		hipLaunchKernelGGL((k_film<1, 0>), grid, dim3(256), 0, st, *F, samples, flags, accum, out, weights, y0, y1, clamp_samples, accumulate);
-	else
-		hipLaunchKernelGGL((k_film<-1, -1>), grid, dim3(256), 0, st, *F, samples, flags, accum, out, weights, y0, y1, clamp_samples,
-		                   accumulate);
-	return hipGetLastError();
-}
-
 hipError_t yafamd_launch_trace_rays(const DevScene *S, int any, const float4 *ro, const float4 *rd, int n, float *t_out,
                                     int *prim_out, int stack_depth, hipStream_t st)
 {
@@ -7068,6 +6689,3 @@ hipError_t yafamd_launch_trace_rays(const DevScene *S, int any, const float4 *ro
 }
 
 }
-
-// the render layers' first-hit pass and film (they call this unit's device functions)
-#include "layers_kernels.h"

@@ -5,17 +5,24 @@
 // Each of them is a closed-form function of the camera ray's first intersection
 // (TiledIntegrator::generateCommonLayers, integrator_tiled.cc:410-630, and the per-sample rules of
 // renderTile, :362-403), so none of it is threaded through the wavefront: a pass of its own regenerates
-// every sample's camera ray (sampleAt / cameraRay, the render's own rays bit for bit), finds the closest
-// hit with the exact traversal, and keeps a 16-byte record per sample; k_layer_film then splats every
-// defined layer from the records with k_film's arithmetic in k_film's order.
+// every sample's camera ray (camera.h sampleAt / cameraRay, the render's own rays bit for bit), finds the
+// closest hit with the exact traversal (trace.h), and keeps a 16-byte record per sample; k_layer_film then
+// splats every defined layer from the records with k_film's arithmetic (filmmath.h) in k_film's order.
 //
-// Not a translation unit of its own: kernels.hip includes this file last (as pkd.hip includes
-// pkd_kernels.h).  The product builds without relocatable device code, and these kernels call that
-// unit's sampleAt, cameraRay and traverse.
+// A translation unit of its own: everything it shares with the path tracer and the film is device-inline code in
+// headers, so the build needs no relocatable device code for it.
 //
 // The first-hit pass and the depth pre-pass keep the whole traversal stack in LDS (k_trace_rays'
 // context: stack bound x block x 4 bytes, no spill column); render.cc refuses the layers of a BVH
 // whose bound exceeds 64 KB of it instead of launching.
+#include <hip/hip_runtime.h>
+#include "devmath.h"
+#include "devscene.h"
+#include "trace.h"
+#include "texeval.h"
+#include "camera.h"
+#include "filmmath.h"
+#include "launch.h"
 
 namespace yafamd
 {

@@ -1,6 +1,6 @@
 // Spot, directional, sun and sphere lights (src/light/light_spot.cc, light_directional.cc, light_sun.cc,
 // light_sphere.cc): their illuminate / illumSample / intersect / emitPhoton bodies with the reference's
-// float expressions.  Included by kernels.hip after devmath.h, rcpExact, shirleyDisk and lv (sphereDir is
+// float expressions.  Included by kernels.hip after devmath.h, rcpExact, shirleyDisk (camera.h) and lv (sphereDir is
 // declared below); only the XL instantiations (DevScene::has_ext_light) call into it.
 //
 // DevLight fields per type (host.cc Scene::createLight, initBoundLight):

@@ -35,7 +35,11 @@
 #include <string>
 #include <vector>
 
+#ifdef PKD_CHECK
+__device__ uint32_t g_pkd_err;   // PK_GUARD's word (pkd_kernels.h), read by yafamd_pkd_check_error below
+#endif
 #include "pkd_kernels.h"
+#include "launch.h"
 
 namespace
 {

@@ -5,9 +5,9 @@
 
 // Checked build (-DPKD_CHECK, tools/pkd_check.py): every computed index is range-checked before
 // use; a failure records the first offending source line and the index is clamped, so a broken
-// invariant shows up as a line number instead of a memory fault.
+// invariant shows up as a line number instead of a memory fault.  The includer defines the word before it
+// includes this file (pkd.hip beside its host reader, tools/pkd_emu.cc): a header defines no __device__ variable.
 #ifdef PKD_CHECK
-__device__ uint32_t g_pkd_err;
 #define PK_GUARD(cond, idx) do { if(!(cond)) { atomicCAS(&g_pkd_err, 0u, (uint32_t)__LINE__); (idx) = 0; } } while(0)
 #else
 #define PK_GUARD(cond, idx) do {} while(0)

@@ -1,7 +1,8 @@
 // GPU driver (see render.h).  Plain C++ against the HIP runtime API; kernels are launched
-// through the extern "C" wrappers at the end of kernels.hip.
+// through the extern "C" wrappers at the end of each device unit, declared in launch.h.
 #include "render.h"
 #include "devmath.h"
+#include "launch.h"
 #include "photonfile.h"
 
 #include <hip/hip_runtime.h>
@@ -19,111 +20,6 @@
 #include <unordered_map>
 
 using namespace yafamd;
-
-extern "C" {
-hipError_t yafamd_launch_camera(const DevScene *S, const DevPaths *P, const DevQueues *Q, const DevCounters *cnt,
-                                const DevJob *jobs, int n_jobs, uint64_t chunk_base, int n, int write_pr, hipStream_t st);
-hipError_t yafamd_launch_surface(const DevScene *S, const DevQueues *Q, const DevCounters *cnt, hipStream_t st);
-hipError_t yafamd_launch_tshadow(const DevScene *S, const DevQueues *Q, const DevCounters *cnt, const DevPaths *P, hipStream_t st);
-hipError_t yafamd_launch_spawn(const DevScene *S, const DevPaths *P, const DevQueues *Q, const DevCounters *cnt, uint32_t s0, int n,
-                               hipStream_t st);
-hipError_t yafamd_launch_combine(const DevScene *S, uint32_t lo, uint32_t hi, int final_level, float4 *samples, const DevJob *jobs,
-                                 int n_jobs, uint64_t chunk_base, hipStream_t st);
-hipError_t yafamd_launch_trace(const DevScene *S, const DevQueues *Q, const DevCounters *cnt, const DevPaths *P,
-                               DevStats *stats, int stack_depth, int *spill, int grid, hipStream_t st);
-int yafamd_trace_block();
-int yafamd_shade_fused();
-unsigned long long yafamd_xl_launches();
-int yafamd_walk_lds_levels(int pm_stack);
-int yafamd_walk_threads(const DevScene *S);
-int yafamd_shade_fused_for(const DevScene *S);
-int yafamd_experiments();
-int yafamd_trace_blocks_per_cu(int lds_scene, int wide, size_t dyn_lds, int defer);
-int yafamd_trace_defer_ok(int n_tris, int max_leaf);
-int yafamd_trace_defer_min_cap();
-int yafamd_shade_blocks_per_cu();
-hipError_t yafamd_launch_shade(const DevScene *S, const DevPaths *Pc, const DevPaths *Pn, const DevQueues *Q,
-                               const DevQueues *Qn, const DevNeeQueue *N, const DevNeeQueue *G, const DevCounters *cnt,
-                               const DevCounters *cnt_next, float4 *samples, const DevJob *jobs, int n_jobs, uint64_t chunk_base,
-                               int stage_it, hipStream_t st);
-int yafamd_shade_stages_for(const DevScene *S);
-int yafamd_shade_stage_errors(uint32_t *out, int n);
-int yafamd_path_eligible(const DevScene *S, int stack_depth, int spill);
-int yafamd_path_blocks_per_cu(const DevScene *S, int stack_depth);
-hipError_t yafamd_launch_path(const DevScene *S, float4 *samples, const DevJob *jobs, int n_jobs, uint64_t chunk_base, uint32_t n,
-                              uint32_t *next, int stack_depth, int grid, hipStream_t st);
-hipError_t yafamd_launch_nee(const DevScene *S, const DevNeeQueue *N, const DevPaths *Pn, const DevQueues *Qn,
-                             const DevCounters *cnt_next, int stack_depth, hipStream_t st);
-int yafamd_nee_blocks_per_cu();
-hipError_t yafamd_photon_emit(const DevScene *S, const PhotonState *P, const PhotonSet *L, uint32_t n_photons, uint32_t h0, uint32_t n_local,
-                              int max_bounces, hipStream_t st);
-hipError_t yafamd_photon_bounce(const DevScene *S, const PhotonState *P, const PhotonSet *L, uint32_t n_photons, uint32_t h0,
-                                uint32_t n_local, int max_bounces, int bounce, int cur, int stack_depth, int *spill, int grid, hipStream_t st);
-hipError_t yafamd_photon_compact(const PhotonState *P, uint32_t *scratch_counts, uint32_t *total_dev, float4 *pos, float4 *dir, float *colb,
-                                 hipStream_t st);
-hipError_t yafamd_launch_gather(const DevScene *S, const DevNeeQueue *G, const DevCounters *cnt_next, float4 *samples,
-                                const DevJob *jobs, int n_jobs, uint64_t chunk_base, const GatherLogDesc *log, hipStream_t st);
-hipError_t yafamd_launch_gather_walk(const DevScene *S, const DevNeeQueue *G, const DevCounters *cnt_next, const GatherLogDesc *log,
-                                     hipStream_t st);
-int yafamd_gather_walk_k();
-size_t yafamd_gather_lds_bytes(const DevScene *S);
-hipError_t yafamd_rad_compact(const PhotonState *P, uint32_t *scratch_counts, uint32_t *total_dev, float4 *a, float4 *b, float4 *c, hipStream_t st);
-hipError_t yafamd_rad_refl(const DevScene *S, float4 *a, float4 *b, float4 *c, const uint32_t *kept, uint32_t n, hipStream_t st);
-hipError_t yafamd_pregather(const DevScene *S, const float4 *a, const float4 *b, const float4 *c, const uint32_t *kept, uint32_t n,
-                            float4 *out_pos, float4 *out_dir, float *out_colb, DevStats *stats, hipStream_t st);
-int yafamd_fg_paths_eligible(const DevScene *S);
-hipError_t yafamd_launch_fg_paths(const DevScene *S, const DevNeeQueue *G, const DevCounters *cnt_next, int stack_depth, int *spill, int grid,
-                                  const FgBatch *B, hipStream_t st);
-hipError_t yafamd_thin_rad_points(const float4 *pos, const float4 *nrm, uint32_t n, float maxrad, uint32_t *kept_out, uint32_t *n_kept,
-                                  int *rounds_out, hipStream_t st, void **scratch);
-void yafamd_thin_scratch_free(void *scratch);
-hipError_t yafamd_rad_grid(const float4 *pos, const float4 *dir, uint32_t n, float lookup_rad, RadGrid *out, hipStream_t st, void **scratch);
-void yafamd_rad_grid_free(void *scratch);
-int yafamd_dfr_eligible(const DevScene *S);
-hipError_t yafamd_dfr_segoff(const DevCounters *cnt, uint32_t n_seg, uint32_t *seg_off, uint32_t *dfr_total, uint32_t cap, uint32_t *overflow,
-                             uint32_t *it_start, hipStream_t st);
-hipError_t yafamd_dfr_accum(const DevScene *S, const DevPaths *P, uint32_t r0, uint32_t r1, uint32_t batch0, float4 *pcol, hipStream_t st);
-hipError_t yafamd_dfr_nee(const DevScene *S, const DevPaths *P, const DevQueues *Q, const DevCounters *cnt, uint32_t r0, uint32_t total, uint32_t *idx,
-                         uint32_t *n_rec, hipStream_t st);
-hipError_t yafamd_dfr_fold(const DevScene *S, float4 *samples, uint32_t n_ctr, const float4 *pcol, hipStream_t st);
-hipError_t yafamd_ray_bin(const DevQueues *Q, const DevCounters *cnt, uint32_t n_seg, uint32_t cap_a, const float *lo, const float *hi,
-                          uint32_t *keys_in, uint32_t *keys_out, uint32_t *iota, uint32_t *perm, void *tmp, size_t *tmp_bytes, hipStream_t st);
-hipError_t yafamd_launch_fg(const DevScene *S, const DevNeeQueue *G, const DevCounters *cnt_next, int stack_depth, int *spill, int grid, float2 *ts_scratch,
-                            hipStream_t st);
-size_t yafamd_gather_lanes(const DevScene *S);
-hipError_t yafamd_build_bvh_gpu(const float *verts_dev, const int *tris_dev, int n, void **nodes_out, void **tris_out,
-                                int *n_nodes, int *depth, int *stack_need, int *ploc_iters, YafBvh8 *w8, hipStream_t st);
-hipError_t yafamd_instance_expand(const DevInstSeg *segs, int n_segs, const float *src_verts, const int *src_tris, const float4 *src_ng,
-                                  const float4 *src_attr, int n_out_verts, int n_out_prims, float *out_verts, int *out_tris, float4 *out_ng,
-                                  float4 *out_attr, float *bounds, hipStream_t st);
-hipError_t yafamd_build_pkd(const float4 *pos_dev, uint32_t n, uint4 *nodes_dev, int *depth_out, hipStream_t st, void **scratch);
-hipError_t yafamd_build_pkd_kd(const float4 *pos_dev, const float4 *dir_dev, const float *colb_dev, uint32_t n, uint4 *nodes_dev, float4 *kpos,
-                               float4 *kdir, float *kcolb, int *depth_out, hipStream_t st, void **scratch);
-void yafamd_pkd_scratch_free(void *scratch);
-hipError_t yafamd_build_pkd_kd_member(const float4 *pos_dev, const float4 *dir_dev, const float *colb_dev, uint32_t n, uint4 *nodes_dev, float4 *kpos,
-                                      float4 *kdir, float *kcolb, int *depth_out, hipStream_t st, void **scratch, int member, int members,
-                                      int *split_level);
-void yafamd_pkd_top_segments(uint32_t n, int level, uint32_t *out);
-void yafamd_pkd_owned_segments(int level, int member, int members, uint32_t *s0, uint32_t *s1);
-hipError_t yafamd_pkd_parent_planes(uint4 *nodes_dev, uint32_t n, hipStream_t st);
-hipError_t yafamd_launch_done_flags(const DevScene *S, const DevJob *jobs, int n_jobs, uint32_t n_pix, uint32_t done_pix, uint8_t *flags,
-                                    hipStream_t st);
-hipError_t yafamd_lpc_seg(const uint32_t *lpc, int W, int spp, int ts, int y0, int y1, uint32_t *seg, hipStream_t st);
-hipError_t yafamd_lpc_prefix(uint32_t *lpc, int W, int spp, int ts, int y0, int y1, const uint32_t *segbase, hipStream_t st);
-hipError_t yafamd_launch_film(const DevFilm *F, const float4 *samples, const uint8_t *flags, float4 *accum, float4 *out,
-                              float *weights, int y0, int y1, float clamp_samples, int accumulate, hipStream_t st);
-hipError_t yafamd_aa_next_pass(const float4 *accum, const float *weights, int W, int H, int tile, const DevAaParams *prm,
-                               float threshold, uint8_t *flags, uint32_t *plist, uint32_t *count, int ry0, int ry1, uint32_t *local_count,
-                               hipStream_t st);
-hipError_t yafamd_launch_trace_rays(const DevScene *S, int any, const float4 *ro, const float4 *rd, int n, float *t_out,
-                                    int *prim_out, int stack_depth, hipStream_t st);
-// render layers (layers_kernels.h)
-hipError_t yafamd_layer_depth_range(const DevScene *S, float *range, int stack_depth, hipStream_t st);
-hipError_t yafamd_launch_layer_hits(const DevScene *S, const DevLayers *L, const DevJob *jobs, int n_jobs, uint64_t chunk_base, int n, int stack_depth,
-                                    hipStream_t st);
-hipError_t yafamd_launch_layer_film(const DevFilm *F, const DevLayers *L, const float4 *prim_ng, const uint8_t *flags, float4 *accum, float4 *out,
-                                    const float *weights, int y0, int y1, float clamp_samples, int accumulate, hipStream_t st);
-}
 
 namespace
 {
@@ -369,7 +265,7 @@ struct GpuRenderer::Impl
 	Buf samples, film, weights, jobs;
 	Buf accum, aa_flags, aa_plist;   // unnormalised film (adaptive passes add to it), nextPass flags, resampled pixels
 	int film_w = 0, film_h = 0;
-	// render layers (layers_kernels.h), allocated only by a render that defines any: first-hit records and the
+	// render layers (layers.hip), allocated only by a render that defines any: first-hit records and the
 	// adv-diffuse-color plane per sample, n_layers film / accumulator planes, the partial planes of the
 	// per-tile callbacks, the index tables and the depth range
 	Buf lay_rec, lay_albedo, lay_accum, lay_film, lay_pfilm, lay_mat, lay_obj, lay_depth;
@@ -2203,7 +2099,7 @@ bool GpuRenderer::Run::ensureLayerBufs(std::initializer_list<std::pair<Buf *, si
 	return true;
 }
 
-// ---- render layers (layers_kernels.h): only a render that defines any allocates or launches anything ----
+// ---- render layers (layers.hip): only a render that defines any allocates or launches anything ----
 bool GpuRenderer::Run::setupLayers()
 {
 	d.n_layers = n_lay;

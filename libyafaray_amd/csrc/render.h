@@ -125,7 +125,7 @@ struct KernelTimes
 	                                 // requests (nee), queries (gather), photon paths (emit, bounce), photons (tree)
 };
 
-// The render layers of a render that defines any beside "combined" (layers_kernels.h; Scene::defineLayer):
+// The render layers of a render that defines any beside "combined" (layers.hip; Scene::defineLayer):
 // the defined kinds in type order and what their values need beside the scene.
 struct LayerParams
 {

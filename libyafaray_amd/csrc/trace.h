@@ -1,6 +1,6 @@
 // BVH traversal of the MI355X path-tracing core (device code only): the ray / box / triangle steps and the
 // loops built from them.  The kernels that run the loops (k_trace, k_path, k_nee, the photon and final-gather
-// kernels, the render layers) and their launch code live in kernels.hip and layers_kernels.h.
+// kernels, the render layers) and their launch code live in kernels.hip and layers.hip.
 //
 // The loops (traverse2, traverse4, traverse4Defer, traceRefill4, traceRefill8, traceLaneRays) share these
 // steps, each defined once here:

@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 def sample_rank(W, H, ts):
     """Rank of every pixel in the GPU's sample enumeration of a one-band render (render.cc jobs,
-    kernels.hip sampleCoord): strips of `ts` columns over the band's rows, left to right, pixels
+    camera.h sampleCoord): strips of `ts` columns over the band's rows, left to right, pixels
     row-major inside a strip.  Chunks complete in this order."""
     y, x = np.mgrid[0:H, 0:W]
     tx = x // ts

@@ -1,5 +1,5 @@
 // Probe: k_film weights for one adaptive pass with synthetic inputs (diagnostics only).
-#include "../libyafaray_amd/csrc/kernels.hip"
+#include "../libyafaray_amd/csrc/film.hip"
 #include <cstdio>
 #include <vector>
 

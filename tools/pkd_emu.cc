@@ -83,6 +83,7 @@ inline uint32_t atomicMin(uint32_t *a, uint32_t v)
 	return o;
 }
 
+uint32_t g_pkd_err;   // PK_GUARD's word: the includer defines it
 #include "../libyafaray_amd/csrc/pkd_kernels.h"
 
 using namespace yafamd_pkd;
