@@ -399,4 +399,47 @@ BvhOutput buildBvh(const BvhInput &in, int leaf_size, int threads)
 	return out;
 }
 
+FlatTable buildFlatTable(const float *nodes, int n_nodes)
+{
+	FlatTable t;
+	for(int node = 0; node < n_nodes; ++node)
+	{
+		const float *o = nodes + 32 * (size_t)node;
+		for(int k = 0; k < 4; ++k)
+		{
+			int child, count;
+			std::memcpy(&child, &o[24 + k], 4);
+			std::memcpy(&count, &o[28 + k], 4);
+			if(child >= 0 || count <= 0) continue;
+			const int first = ~child;
+			if(first + count > kFlatMaxTris) return FlatTable{};
+			const uint64_t bits = (count == 64 ? ~0ull : ((1ull << count) - 1ull)) << first;
+			FlatLeaf r;
+			for(int a = 0; a < 3; ++a) { r.lo[a] = o[8 * a + k]; r.hi[a] = o[8 * a + 4 + k]; }
+			r.bits_lo = (uint32_t)bits;
+			r.bits_hi = (uint32_t)(bits >> 32);
+			t.rec.push_back(r);
+		}
+	}
+	// (the slots of distinct leaves are disjoint, so the low word's lowest bit orders them)
+	std::stable_sort(t.rec.begin(), t.rec.end(), [](const FlatLeaf &a, const FlatLeaf &b) {
+		const uint64_t x = ((uint64_t)a.bits_hi << 32) | a.bits_lo, y = ((uint64_t)b.bits_hi << 32) | b.bits_lo;
+		return (x & (~x + 1)) < (y & (~y + 1));
+	});
+	t.n = (int)t.rec.size();
+	for(const FlatLeaf &r : t.rec)
+	{
+		if(!r.bits_hi) ++t.n_lo;
+		if(r.bits_lo) ++t.n_mid;
+	}
+	t.n_mid = std::max(t.n_mid, t.n_lo);
+	t.rec.push_back(FlatLeaf{});
+	return t;
+}
+
+bool flatEligible(int n_tris, int n_leaves, bool forced)
+{
+	return n_tris > 0 && n_tris <= kFlatMaxTris && n_leaves > 0 && n_leaves <= (forced ? kFlatMaxTris : kFlatMaxLeaves);
+}
+
 } // namespace yafamd

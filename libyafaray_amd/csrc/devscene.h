@@ -473,6 +473,8 @@ struct DevQueues
 	int nee_grid;          // k_nee workgroups (0 or >= n_seg: one per segment; fewer: a workgroup walks several segments)
 	int trace_defer;       // k_trace's plain no-spill BVH4 loop over an LDS-resident scene: 0 = leaf triangles tested inside
 	                       // the visit; n > 0 = recorded in per-lane LDS lists of n leaf entries and tested afterwards
+	int trace_flat;        // the same loop's flat scan (trace.h traverseFlat; takes precedence over trace_defer): 0 = off, else
+	                       // bvh.h flatPack of the scene's leaf table, which the launch passes as a kernel argument
 };
 
 // DevQueues::trace_part.  TRACE_CLOSEST reads no shadow count (k_nee may be writing it beside the launch);

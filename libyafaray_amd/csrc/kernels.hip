@@ -449,11 +449,15 @@ __device__ __forceinline__ void waveSortWindow(WaveSort &W, const uint32_t (&key
 // SORT: ray-stream sorting of each wave's window (above)
 // W8: the refill loop over the BVH8 (S.nodes8; global-memory scenes without transparent shadows)
 // DEFER: the plain loop's BVH4 traversal with deferred leaf tests (traverse4Defer; Q.trace_defer = the lists' capacity)
-template<bool LDS_SCENE, bool WIDE, bool TS, bool SPILL = true, bool STATS = true, bool SORT = false, bool W8 = false, bool DEFER = false>
+// FLAT: the plain loop's flat scan of the scene's leaf table (traverseFlat; Q.trace_flat, flat_tab = the table; only the
+// triangles are staged in LDS, at their usual place)
+template<bool LDS_SCENE, bool WIDE, bool TS, bool SPILL = true, bool STATS = true, bool SORT = false, bool W8 = false, bool DEFER = false,
+         bool FLAT = false>
 __global__ void __launch_bounds__(kTraceBlock) YAF_TRACE_ATTR k_trace(DevScene S, DevQueues Q, DevCounters cnt, DevPaths P,
-                                                      DevStats *stats, int stack_depth, int *spill)
+                                                      DevStats *stats, int stack_depth, int *spill, const float4 *__restrict__ flat_tab)
 {
 	static_assert(!DEFER || (LDS_SCENE && WIDE && !TS && !SPILL && !SORT && !W8), "deferred leaf tests: the plain no-spill BVH4 loop of LDS-resident scenes");
+	static_assert(!FLAT || (LDS_SCENE && WIDE && !TS && !SPILL && !SORT && !W8 && !DEFER), "flat scan: the plain no-spill BVH4 loop of LDS-resident scenes");
 	extern __shared__ float4 smem[];
 	int *stack = reinterpret_cast<int *>(smem);
 	TraceCtx C;
@@ -467,7 +471,8 @@ __global__ void __launch_bounds__(kTraceBlock) YAF_TRACE_ATTR k_trace(DevScene S
 	{
 		float4 *lds_nodes = smem + (stack_depth * kTraceBlock) / 4;
 		float4 *lds_tris = lds_nodes + S.node_f4 * S.n_nodes;
-		for(int k = threadIdx.x; k < S.node_f4 * S.n_nodes; k += blockDim.x) lds_nodes[k] = S.nodes[k];
+		if constexpr(!FLAT)
+			for(int k = threadIdx.x; k < S.node_f4 * S.n_nodes; k += blockDim.x) lds_nodes[k] = S.nodes[k];
 		for(int k = threadIdx.x; k < 3 * S.n_tris; k += blockDim.x) lds_tris[k] = S.tris[k];
 		__syncthreads();
 		C.nodes = lds_nodes;
@@ -532,7 +537,8 @@ __global__ void __launch_bounds__(kTraceBlock) YAF_TRACE_ATTR k_trace(DevScene S
 				float t;
 				int prim;
 				const float tmax = (tw >= 0.f) ? tw : __builtin_huge_valf();
-				if constexpr(DEFER) traverse4Defer<false, STATS>(C, dlist, Q.trace_defer, o, d, tmin, tmax, t, prim, visits, tests);
+				if constexpr(FLAT) traverseFlat<false, STATS>(C, flat_tab, Q.trace_flat, o, d, tmin, tmax, t, prim, visits, tests);
+				else if constexpr(DEFER) traverse4Defer<false, STATS>(C, dlist, Q.trace_defer, o, d, tmin, tmax, t, prim, visits, tests);
 				else traverse<false, WIDE, SPILL, false, STATS>(C, o, d, tmin, tmax, t, prim, visits, tests);
 				raySt(&Q.hit_t[i], t);
 				raySt(&Q.hit_prim[i], prim);
@@ -557,6 +563,7 @@ __global__ void __launch_bounds__(kTraceBlock) YAF_TRACE_ATTR k_trace(DevScene S
 				occ = traverse<true, WIDE, SPILL, true>(C, xyz(od), xyz(dd), od.w, dd.w, t, prim, visits, tests, &L);
 				Q.ts_n[k] = occ ? 0 : L.n;
 			}
+			else if constexpr(FLAT) occ = traverseFlat<true, STATS>(C, flat_tab, Q.trace_flat, xyz(od), xyz(dd), 0.f, dd.w, t, prim, visits, tests);
 			else if constexpr(DEFER) occ = traverse4Defer<true, STATS>(C, dlist, Q.trace_defer, xyz(od), xyz(dd), 0.f, dd.w, t, prim, visits, tests);
 			else occ = traverse<true, WIDE, SPILL, false, STATS>(C, xyz(od), xyz(dd), 0.f, dd.w, t, prim, visits, tests);
 			// (opaque shadows: the NEE entry index rides in sh_o.w)
@@ -5991,7 +5998,7 @@ hipError_t yafamd_launch_camera(const DevScene *S, const DevPaths *P, const DevQ
 }
 
 hipError_t yafamd_launch_trace(const DevScene *S, const DevQueues *Q, const DevCounters *cnt, const DevPaths *P,
-                               DevStats *stats, int stack_depth, int *spill, int grid, hipStream_t st)
+                               DevStats *stats, int stack_depth, int *spill, const float4 *flat_tab, int grid, hipStream_t st)
 {
 	const size_t stack_bytes = (size_t)stack_depth * kTraceBlock * sizeof(int);
 	const bool wide = S->node_f4 == 8;
@@ -6004,10 +6011,10 @@ hipError_t yafamd_launch_trace(const DevScene *S, const DevQueues *Q, const DevC
 		const size_t bytes8 = stack_bytes + (size_t)S->lds_top8 * kTop8Stride * sizeof(float4);
 		if(S->trace_stats)
 			hipLaunchKernelGGL((k_trace<false, true, false, true, true, false, true>), dim3(grid), dim3(kTraceBlock), bytes8, st, *S, *Q, *cnt, *P, stats,
-			                   stack_depth, spill);
+			                   stack_depth, spill, flat_tab);
 		else
 			hipLaunchKernelGGL((k_trace<false, true, false, true, false, false, true>), dim3(grid), dim3(kTraceBlock), bytes8, st, *S, *Q, *cnt, *P, stats,
-			                   stack_depth, spill);
+			                   stack_depth, spill, flat_tab);
 		return hipGetLastError();
 	}
 #ifdef YAF_EXPERIMENTS
@@ -6017,7 +6024,7 @@ hipError_t yafamd_launch_trace(const DevScene *S, const DevQueues *Q, const DevC
 		return hipGetLastError();
 	}
 #endif
-#define YAF_TRACE_LAUNCH(L, W, T, SP) hipLaunchKernelGGL((k_trace<L, W, T, SP>), dim3(grid), dim3(kTraceBlock), bytes, st, *S, *Q, *cnt, *P, stats, stack_depth, spill)
+#define YAF_TRACE_LAUNCH(L, W, T, SP) hipLaunchKernelGGL((k_trace<L, W, T, SP>), dim3(grid), dim3(kTraceBlock), bytes, st, *S, *Q, *cnt, *P, stats, stack_depth, spill, flat_tab)
 	// no spill column: the LDS levels hold the whole stack bound (LDS-resident scenes)
 	const bool nospill = spill == nullptr;
 	if(S->tr_shad)
@@ -6038,14 +6045,27 @@ hipError_t yafamd_launch_trace(const DevScene *S, const DevQueues *Q, const DevC
 		{
 			if(S->trace_stats)
 				hipLaunchKernelGGL((k_trace<true, true, false, false, true, true>), dim3(grid), dim3(kTraceBlock), bytes, st, *S, *Q, *cnt, *P, stats,
-				                   stack_depth, spill);
+				                   stack_depth, spill, flat_tab);
 			else
 				hipLaunchKernelGGL((k_trace<true, true, false, false, false, true>), dim3(grid), dim3(kTraceBlock), bytes, st, *S, *Q, *cnt, *P, stats,
-				                   stack_depth, spill);
+				                   stack_depth, spill, flat_tab);
 		}
 		else
 #endif
-		if(nospill && wide && Q->trace_defer > 0)
+		if(nospill && wide && Q->trace_flat > 0)
+		{
+			// the flat scan (traverseFlat): the same LDS layout; the caller sets trace_flat only with the scene's
+			// leaf table (bvh.h buildFlatTable)
+			const int fn = Q->trace_flat & 0xff, fn_lo = (Q->trace_flat >> 8) & 0xff, fn_mid = (Q->trace_flat >> 16) & 0xff;
+			if(!flat_tab || S->n_tris > kFlatMaxTris || fn > kFlatMaxTris || fn_lo > fn_mid || fn_mid > fn) return hipErrorInvalidValue;
+			if(S->trace_stats)
+				hipLaunchKernelGGL((k_trace<true, true, false, false, true, false, false, false, true>), dim3(grid), dim3(kTraceBlock), bytes, st, *S, *Q, *cnt, *P, stats,
+				                   stack_depth, spill, flat_tab);
+			else
+				hipLaunchKernelGGL((k_trace<true, true, false, false, false, false, false, false, true>), dim3(grid), dim3(kTraceBlock), bytes, st, *S, *Q, *cnt, *P, stats,
+				                   stack_depth, spill, flat_tab);
+		}
+		else if(nospill && wide && Q->trace_defer > 0)
 		{
 			// deferred leaf tests (traverse4Defer): the lists follow the scene.  The caller sets trace_defer only
 			// for trees whose leaves fit an entry (yafamd_trace_defer_ok with the builder's largest leaf)
@@ -6053,14 +6073,14 @@ hipError_t yafamd_launch_trace(const DevScene *S, const DevQueues *Q, const DevC
 			bytes += (size_t)Q->trace_defer * kTraceBlock * sizeof(uint16_t);
 			if(S->trace_stats)
 				hipLaunchKernelGGL((k_trace<true, true, false, false, true, false, false, true>), dim3(grid), dim3(kTraceBlock), bytes, st, *S, *Q, *cnt, *P, stats,
-				                   stack_depth, spill);
+				                   stack_depth, spill, flat_tab);
 			else
 				hipLaunchKernelGGL((k_trace<true, true, false, false, false, false, false, true>), dim3(grid), dim3(kTraceBlock), bytes, st, *S, *Q, *cnt, *P, stats,
-				                   stack_depth, spill);
+				                   stack_depth, spill, flat_tab);
 		}
 		else if(nospill && wide && !S->trace_stats)
 			hipLaunchKernelGGL((k_trace<true, true, false, false, false>), dim3(grid), dim3(kTraceBlock), bytes, st, *S, *Q, *cnt, *P, stats,
-			                   stack_depth, spill);
+			                   stack_depth, spill, flat_tab);
 		else if(nospill) { if(wide) YAF_TRACE_LAUNCH(true, true, false, false); else YAF_TRACE_LAUNCH(true, false, false, false); }
 		else if(wide) YAF_TRACE_LAUNCH(true, true, false, true);
 		else YAF_TRACE_LAUNCH(true, false, false, true);
@@ -6070,15 +6090,15 @@ hipError_t yafamd_launch_trace(const DevScene *S, const DevQueues *Q, const DevC
 	{
 		if(S->trace_stats)
 			hipLaunchKernelGGL((k_trace<false, true, false, true, true, true>), dim3(grid), dim3(kTraceBlock), bytes, st, *S, *Q, *cnt, *P, stats,
-			                   stack_depth, spill);
+			                   stack_depth, spill, flat_tab);
 		else
 			hipLaunchKernelGGL((k_trace<false, true, false, true, false, true>), dim3(grid), dim3(kTraceBlock), bytes, st, *S, *Q, *cnt, *P, stats,
-			                   stack_depth, spill);
+			                   stack_depth, spill, flat_tab);
 	}
 #endif
 	else if(wide && !S->trace_stats)
 		hipLaunchKernelGGL((k_trace<false, true, false, true, false>), dim3(grid), dim3(kTraceBlock), bytes, st, *S, *Q, *cnt, *P, stats,
-		                   stack_depth, spill);
+		                   stack_depth, spill, flat_tab);
 	else if(wide) YAF_TRACE_LAUNCH(false, true, false, true);
 	else YAF_TRACE_LAUNCH(false, false, false, true);
 #undef YAF_TRACE_LAUNCH

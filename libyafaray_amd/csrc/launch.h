@@ -22,7 +22,7 @@ hipError_t yafamd_launch_spawn(const yafamd::DevScene *S, const yafamd::DevPaths
 hipError_t yafamd_launch_combine(const yafamd::DevScene *S, uint32_t lo, uint32_t hi, int final_level, float4 *samples, const yafamd::DevJob *jobs,
                                  int n_jobs, uint64_t chunk_base, hipStream_t st);
 hipError_t yafamd_launch_trace(const yafamd::DevScene *S, const yafamd::DevQueues *Q, const yafamd::DevCounters *cnt, const yafamd::DevPaths *P,
-                               yafamd::DevStats *stats, int stack_depth, int *spill, int grid, hipStream_t st);
+                               yafamd::DevStats *stats, int stack_depth, int *spill, const float4 *flat_tab, int grid, hipStream_t st);
 int yafamd_trace_block();
 int yafamd_shade_fused();
 unsigned long long yafamd_xl_launches();

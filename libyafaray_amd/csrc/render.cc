@@ -34,6 +34,23 @@ int traceDeferCap(int cap)
 	if(const char *e = std::getenv("YAFARAY_AMD_TRACE_DEFER"); e && *e) on = *e != '0';
 	return on ? cap : 0;
 }
+// DevQueues::trace_flat of a scene whose leaf table packs to `pack` (bvh.h flatPack; 0: no table): the flat scan is a
+// member of the deferred family, so it runs only where the lists would (`defer_cap` = traceDeferCap's answer > 0),
+// and an explicit YAFARAY_AMD_TRACE_DEFER_CAP asks for the lists (a capacity means nothing to the scan).
+// YAFARAY_AMD_TRACE_FLAT=0: the lists; =1: the scan whatever the leaf count; unset: the scan up to kFlatMaxLeaves
+// leaves.  Read per render and per traceQueued call.
+int traceFlatPack(int pack, int defer_cap)
+{
+	if(pack == 0 || defer_cap == 0) return 0;
+	if(const char *e = std::getenv("YAFARAY_AMD_TRACE_DEFER_CAP"); e && *e) return 0;
+	bool forced = false;
+	if(const char *e = std::getenv("YAFARAY_AMD_TRACE_FLAT"); e && *e)
+	{
+		if(*e == '0') return 0;
+		forced = true;
+	}
+	return flatEligible(kFlatMaxTris, pack & 0xff, forced) ? pack : 0;
+}
 
 // The renderer's device made current for the duration of a call; the caller's device is restored
 // (several renderers of one process, on different devices, may be driven from one thread).
@@ -257,6 +274,8 @@ struct GpuRenderer::Impl
 	int n_nodes = 0, n_tris = 0, n_mats = 0, n_lights = 0, depth = 0, stack_depth = 32, node_f4 = 4;
 	int lds_stack = 32;    // k_trace stack levels held in LDS; levels [lds_stack, stack_depth) spill to `spill`
 	int trace_defer = 0;   // k_trace's deferred leaf tests: the per-lane list's capacity for this scene (0: not eligible)
+	Buf flat_tab;          // k_trace's flat scan: the scene's leaf table (bvh.h FlatLeaf records + one spare), or empty
+	int trace_flat = 0;    // flatPack of that table (0: no table: the scene is not deferred-eligible or has > 64 triangles)
 	Buf spill;
 	bool scene_in_lds = false;
 	int lds_top = 0;   // BVH4 in global memory: nodes k_trace stages in LDS (the top treelet)
@@ -804,6 +823,25 @@ bool GpuRenderer::upload(HostScene &hs)
 				auto fits = [&](int c) { return yafamd_trace_blocks_per_cu(1, 1, dyn + (size_t)c * yafamd_trace_block() * 2, 1) >= per_cu; };
 				while(cap > min_cap && !fits(cap)) cap = std::max(min_cap, cap - 2);
 				if(fits(cap)) d.trace_defer = cap;
+			}
+		}
+		// The flat scan (trace.h traverseFlat): a deferred-eligible scene of at most kFlatMaxTris triangles gets its
+		// leaf table (the host tree's nodes, or the device-built ones read back: 128 B per node).  Whether a launch
+		// uses it is read per render (traceFlatPack); the kernel has the interleaved kernel's LDS layout and at
+		// most its registers, so the grid above holds.
+		d.trace_flat = 0;
+		d.flat_tab.release();
+		if(d.trace_defer > 0 && d.n_tris <= kFlatMaxTris)
+		{
+			std::vector<float> nodes((size_t)32 * d.n_nodes);
+			if(hs.gpu_build) HIPCHECK(hipStreamSynchronize(d.stream));
+			if(hs.gpu_build) HIPCHECK(hipMemcpy(nodes.data(), d.nodes.p, nodes.size() * sizeof(float), hipMemcpyDeviceToHost));
+			else std::copy(hs.bvh.nodes.begin(), hs.bvh.nodes.begin() + nodes.size(), nodes.begin());
+			const FlatTable ft = buildFlatTable(nodes.data(), d.n_nodes);
+			if(flatEligible(d.n_tris, ft.n, true))
+			{
+				if(!allocCopy(log_, d.flat_tab, ft.rec.data(), ft.rec.size())) return false;
+				d.trace_flat = flatPack(ft);
 			}
 		}
 		if(const char *e = getenv("YAFARAY_AMD_TRACE_GRID")) d.trace_grid = std::max(1, atoi(e));
@@ -1814,6 +1852,7 @@ struct Schedule
 	bool ov_shadow = false;                        // the shadow part beside the side stream's closest part
 	int ov_shadow_grid = 0;
 	bool defer_it0 = false;                        // k_trace's deferred leaf lists in iteration 0 too
+	bool flat_it0 = false;                         // k_trace's flat scan in iteration 0 too
 	bool ray_bin = false;                          // the bounce rays sorted before k_trace
 	int nee_trace_stack = 0;                       // > 0: k_nee traces its shadow rays in place, with this LDS stack
 	bool lpc_on = false;                           // the one-thread light pick (count run or deferred pick per pass)
@@ -2505,6 +2544,10 @@ bool GpuRenderer::Run::decideSchedule()
 	// YAFARAY_AMD_TRACE_DEFER_IT0=1 uses the lists there too (A/B)
 	d.Q[0].trace_defer = d.Q[1].trace_defer = traceDeferCap(d.trace_defer);
 	if(const char *e = std::getenv("YAFARAY_AMD_TRACE_DEFER_IT0"); e && *e) sch.defer_it0 = *e != '0';
+	// the flat scan instead of the lists where the render's switches choose it (traceFlatPack); iteration 0 has
+	// its own switch, YAFARAY_AMD_TRACE_FLAT_IT0 (profiles/c2_trace_flat.md)
+	d.Q[0].trace_flat = d.Q[1].trace_flat = traceFlatPack(d.trace_flat, d.Q[0].trace_defer);
+	if(const char *e = std::getenv("YAFARAY_AMD_TRACE_FLAT_IT0"); e && *e) sch.flat_it0 = *e != '0';
 	// The megakernel (k_path, kernels.hip; opt-in YAFARAY_AMD_PATH=mega) for scenes whose BVH, stack
 	// and tables live in LDS and need none of the wavefront-only stages (EXT shading, transparent
 	// shadows, photon maps, AO): one lane per sample, the same functions in the same order, the film
@@ -2569,7 +2612,7 @@ bool GpuRenderer::Run::startClock()
 bool GpuRenderer::Run::launchShadowBesideClosest(const DevQueues &qc, int cur)
 {
 	SideSync side{d.side};   // a failed launch: leave no side-stream work behind
-	PROF(KK_TRACE, yafamd_launch_trace(&S, &qc, &cnt[cur], &d.P[cur], run_stats + d.trace_grid, d.lds_stack, nullptr, sch.ov_shadow_grid,
+	PROF(KK_TRACE, yafamd_launch_trace(&S, &qc, &cnt[cur], &d.P[cur], run_stats + d.trace_grid, d.lds_stack, nullptr, (const float4 *)d.flat_tab.p, sch.ov_shadow_grid,
 	                                    d.stream));
 	HIPCHECK(hipStreamWaitEvent(d.stream, d.ev_join, 0));
 	side.ok = true;
@@ -2596,7 +2639,7 @@ bool GpuRenderer::Run::launchNeeBesideNextClosest(int cur)
 	HIPCHECK(hipStreamWaitEvent(d.side, d.ev_fork, 0));
 	SideSync side{d.side};   // a failed launch: leave no side-stream work behind
 	PROF_ON(KK_TRACE, d.side, yafamd_launch_trace(&S, &qn, &cnt[cur ^ 1], &d.P[cur ^ 1], run_stats, d.lds_stack, (int *)d.spill.p,
-	                                              sch.ov_trace_grid, d.side));
+	                                              (const float4 *)d.flat_tab.p, sch.ov_trace_grid, d.side));
 	HIPCHECK(hipEventRecord(d.ev_join, d.side));
 	PROF(KK_NEE, yafamd_launch_nee(&S, &d.N, &d.P[cur ^ 1], &qnee, &cnt[cur ^ 1], sch.nee_trace_stack, d.stream));
 	// (the early shadow part: the next iteration joins, after its shadow launch)
@@ -2679,6 +2722,7 @@ bool GpuRenderer::Run::iterate(uint64_t base)
 		qc.perm = nullptr;
 		qc.trace_part = closest_done ? TRACE_SHADOW : TRACE_BOTH;
 		if(it == 0 && !sch.defer_it0) qc.trace_defer = 0;
+		if(it == 0 && !sch.flat_it0) qc.trace_flat = 0;
 		// the side stream's closest part is still running: the shadow part goes beside it, then the join
 		const bool join_pending = closest_done && sch.ov_shadow;
 		closest_done = false;
@@ -2696,7 +2740,7 @@ bool GpuRenderer::Run::iterate(uint64_t base)
 		}
 		else
 			PROF(KK_TRACE, yafamd_launch_trace(&S, &qc, &cnt[cur], &d.P[cur], run_stats, d.lds_stack, (int *)d.spill.p,
-			                                    S.tr_shad ? d.trace_grid_bvh4 : d.trace_grid, d.stream));
+			                                    (const float4 *)d.flat_tab.p, S.tr_shad ? d.trace_grid_bvh4 : d.trace_grid, d.stream));
 		// material-shade dispatch for textured / smooth scenes: surface attributes + shader nodes
 		// of every hit, before k_shade reads them
 		// transparent shadows: filter colours of the transparent surfaces the shadow rays crossed
@@ -2930,7 +2974,7 @@ int GpuRenderer::Run::runDeferredPick(uint64_t n_total, int pass_spp, size_t n_c
 		qs.ray_tt = nullptr;
 		qs.perm = nullptr;
 		qs.tmin_dflt = S.ray_min_dist;
-		PROF(KK_TRACE, yafamd_launch_trace(&S, &qs, &cnt[0], &d.P[0], run_stats, d.lds_stack, (int *)d.spill.p, d.trace_grid, d.stream));
+		PROF(KK_TRACE, yafamd_launch_trace(&S, &qs, &cnt[0], &d.P[0], run_stats, d.lds_stack, (int *)d.spill.p, (const float4 *)d.flat_tab.p, d.trace_grid, d.stream));
 		// every sample's terms of this batch, iteration range by iteration range (one record per sample and
 		// iteration; the ranges increase with the slots, so the additions keep the one-pass order)
 		const uint32_t r1 = std::min<uint64_t>((uint64_t)r0 + batch, total_slots);
@@ -3587,13 +3631,14 @@ bool GpuRenderer::traceRaysQueued(const float *closest, int n_closest, const flo
 		Q.perm = nullptr;
 		Q.trace_part = part;
 		Q.trace_defer = traceDeferCap(d.trace_defer);
+		Q.trace_flat = traceFlatPack(d.trace_flat, Q.trace_defer);
 		DevCounters cnt{};
 		cnt.n_active = (uint32_t *)b_na.p;
 		cnt.n_shadow = (uint32_t *)b_ns.p;
 		DevPaths P{};
 		P.occ = (uint8_t *)b_occ.p;
 		ok = hipMemsetAsync(b_stats.p, 0, sizeof(DevStats) * (size_t)grid, d.stream) == hipSuccess &&
-		     yafamd_launch_trace(&S, &Q, &cnt, &P, (DevStats *)b_stats.p, d.lds_stack, (int *)d.spill.p, grid, d.stream) == hipSuccess &&
+		     yafamd_launch_trace(&S, &Q, &cnt, &P, (DevStats *)b_stats.p, d.lds_stack, (int *)d.spill.p, (const float4 *)d.flat_tab.p, grid, d.stream) == hipSuccess &&
 		     hipStreamSynchronize(d.stream) == hipSuccess;
 		if(!ok) log_.error("GPU: traceQueued: launch failed");
 		ok = ok && hipMemcpy(ht.data(), b_ht.p, NA * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess &&

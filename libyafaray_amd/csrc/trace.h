@@ -2,8 +2,8 @@
 // loops built from them.  The kernels that run the loops (k_trace, k_path, k_nee, the photon and final-gather
 // kernels, the render layers) and their launch code live in kernels.hip and layers.hip.
 //
-// The loops (traverse2, traverse4, traverse4Defer, traceRefill4, traceRefill8, traceLaneRays) share these
-// steps, each defined once here:
+// The loops (traverse2, traverse4, traverse4Defer, traverseFlat, traceRefill4, traceRefill8, traceLaneRays) share
+// these steps, each defined once here:
 //
 //   rayPrep      the ray's inverse direction (with the 1e-20 clamp), o / d, the near / far plane selectors
 //                and the padded entry distance box_t0
@@ -20,12 +20,13 @@
 // the child / count / leaf bookkeeping of a BVH4 visit, the per-lane leaf span, the pushes after the
 // network and the refill loops' queue fetch and write-back (profiles/trace_refactor.md).  Every ray of
 // every loop runs the same visits, culling, leaf order and exits as traverse4 (traverse4Defer: a superset
-// of the visits), so hits are identical.
+// of the visits; traverseFlat: every leaf box, no inner visit), so hits are identical.
 //
 // Compiled with -ffp-contract=off: every float expression keeps the reference's order.
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include "bvh.h"
 #include "devmath.h"
 #include "devscene.h"
 
@@ -677,6 +678,100 @@ __device__ bool traverse4Defer(const TraceCtx &C, uint16_t *list, int cap, V3 o,
 		}
 		n = 0;
 		if(node < 0) break;
+	}
+	return prim_best >= 0;
+}
+
+// The flat scan (LDS-resident BVH4 over at most kFlatMaxTris triangles, no spill column, opaque shadows;
+// DevQueues::trace_flat): no box traversal at all.
+//   phase 1: every leaf box of the scene (bvh.h FlatLeaf, built by upload()) against the ray's
+//            [box_t0, slackOf(tmax)] interval, in a loop that is the same for every lane: no stack, no child
+//            order, no per-lane address.  The record index is wave-uniform and the table is read through the
+//            constant address space, so a record arrives as one scalar load for the 64 lanes, two records
+//            requested per trip.  Per axis t_a = fma(lo, id, -oid),
+//            t_b = fma(hi, id, -oid), near = min, far = max: by the monotonicity argument above slab4 these
+//            are the values slab4's sign-selected planes give, so a box is hit here exactly when slab4 hits it
+//            with slack_t = slackOf(tmax).  A hit box ORs the leaf's triangle slots into the lane's 64-bit
+//            mask; the table is ordered so that each of the three loops knows which mask words it touches.
+//   phase 2: the mask's triangles, lowest slot first, through triTest and traverse4's hit predicates; an
+//            any-hit ray ends at its first hit.  One round per ray: t_best never culls a box.
+// A leaf's stored box lies inside its ancestors' stored boxes (every box is its subtree's bounds plus a pad
+// that grows with the bounds, bvh.cc padBox), so the hit leaves are a superset of the leaves either tree loop reaches with the same interval;
+// closest hits are the minimum over (t, primitive) of the tested triangles, any hits a boolean: the results
+// are traverse4's.  A ray's tests depend on the ray and the scene alone.  STATS: a "visit" is four boxes.
+typedef float f32x8_t __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ f32x8_t flatLd(const float4 *__restrict__ tab, int i)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+	typedef const f32x8_t __attribute__((address_space(4))) *ConstRec;
+	return ((ConstRec)tab)[__builtin_amdgcn_readfirstlane(i)];
+#else   // (host pass of the single-source compile: never executed)
+	return reinterpret_cast<const f32x8_t *>(tab)[i];
+#endif
+}
+// one record against the ray: WORDS bit 0 = the leaf has slots in the low mask word, bit 1 = in the high one
+template<int WORDS>
+__device__ __forceinline__ void flatBox(const f32x8_t &r, const RayPrep &R, float t_far, uint32_t &m_lo, uint32_t &m_hi)
+{
+	const float ax = __builtin_fmaf(r[0], R.id.x, -R.oid.x), bx = __builtin_fmaf(r[4], R.id.x, -R.oid.x);
+	const float ay = __builtin_fmaf(r[1], R.id.y, -R.oid.y), by = __builtin_fmaf(r[5], R.id.y, -R.oid.y);
+	const float az = __builtin_fmaf(r[2], R.id.z, -R.oid.z), bz = __builtin_fmaf(r[6], R.id.z, -R.oid.z);
+	const float lo = fmaxf(fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz)), R.box_t0);
+	const float hi = fminf(fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz)), t_far);
+	const bool h = lo <= hi;
+	if(WORDS & 1) m_lo |= h ? __float_as_uint(r[3]) : 0u;
+	if(WORDS & 2) m_hi |= h ? __float_as_uint(r[7]) : 0u;
+}
+// records [i0, i1), two per trip: both records are requested before the first is tested
+template<int WORDS>
+__device__ __forceinline__ void flatScan(const float4 *__restrict__ tab, int i0, int i1, const RayPrep &R, float t_far, uint32_t &m_lo,
+                                         uint32_t &m_hi)
+{
+	int i = i0;
+	for(; i + 1 < i1; i += 2)
+	{
+		const f32x8_t r0 = flatLd(tab, i), r1 = flatLd(tab, i + 1);
+		flatBox<WORDS>(r0, R, t_far, m_lo, m_hi);
+		flatBox<WORDS>(r1, R, t_far, m_lo, m_hi);
+	}
+	if(i < i1) flatBox<WORDS>(flatLd(tab, i), R, t_far, m_lo, m_hi);
+}
+template<bool ANY, bool STATS>
+__device__ bool traverseFlat(const TraceCtx &C, const float4 *__restrict__ tab, int flat, V3 o, V3 d, float tmin, float tmax, float &t_best,
+                             int &prim_best, uint32_t &visits, uint32_t &tests)
+{
+	const RayPrep R = rayPrep(o, d, tmin, ANY);
+	t_best = tmax;
+	prim_best = -1;
+	// ---- phase 1: the leaf boxes (flat = bvh.h flatPack: n | n_lo << 8 | n_mid << 16) ----
+	const int n = flat & 0xff, n_lo = (flat >> 8) & 0xff, n_mid = (flat >> 16) & 0xff;
+	const float t_far = slackOf(tmax);
+	uint32_t m_lo = 0, m_hi = 0;
+	flatScan<1>(tab, 0, n_lo, R, t_far, m_lo, m_hi);
+	flatScan<3>(tab, n_lo, n_mid, R, t_far, m_lo, m_hi);
+	flatScan<2>(tab, n_mid, n, R, t_far, m_lo, m_hi);
+	if(STATS) TRACE_STAT(visits += (uint32_t)(n + 3) >> 2);
+	// ---- phase 2: the pending triangles, one per trip; the bit index is the triangle slot ----
+	uint64_t m = ((uint64_t)m_hi << 32) | m_lo;
+	while(m)
+	{
+		const int q = __builtin_ctzll(m);
+		m &= m - 1ull;
+		if(STATS) TRACE_STAT(++tests);
+		const float4 *tp = C.tris + 3 * q;
+		const float4 ta = tp[0], tb = tp[1], tc = tp[2];
+		const float t = triTest(ta, tb, tc, o, d);
+		if(t == -1.f) continue;
+		const int prim = __float_as_int(tb.w);
+		if(ANY)
+		{
+			if(HIT_ANY(t, tmax)) { t_best = t; prim_best = prim; break; }
+		}
+		else if(HIT_CLOSER(t, prim, tmin, t_best, prim_best))
+		{
+			t_best = t;
+			prim_best = prim;
+		}
 	}
 	return prim_best >= 0;
 }

@@ -13,7 +13,11 @@
 // per wave (DESIGN §5 "C2 k_trace instruction budget"): setup 91, visit 84 + the order network (60 closest, 30
 // any-hit), triangle test 97; the deferred loop adds kAppend per visit (four list stores and the slot
 // arithmetic) and kTrip per triangle trip (the leaf cursor).
-// The model asserts that both loops return the same (t, primitive) / occlusion for every ray.
+// The flat scan (traverseFlat) has no box traversal: every ray tests the L leaf boxes of the scene's leaf table
+// (bvh.cc buildFlatTable) against [box_t0, slack(tmax)] at kFlatBox VALU each, in a wave-uniform loop, then its
+// pending triangles lowest slot first (kTri per trip; no leaf cursor).  The last line prints the lists' box
+// traversal per wave on the whole mix and the leaf count at which kFlatBox L reaches it (bvh.h kFlatMaxLeaves).
+// The model asserts that all loops return the same (t, primitive) / occlusion for every ray.
 #include "../libyafaray_amd/csrc/bvh.h"
 
 #include <algorithm>
@@ -28,6 +32,7 @@
 using namespace yafamd;
 
 constexpr int kSetup = 91, kVisit = 84, kOrderClosest = 60, kOrderAny = 30, kTri = 97, kAppend = 12, kTrip = 6;
+constexpr int kFlatBox = 19;   // 6 FMA, 6 min / max, max3 + max, min3 + min, compare, select + OR (from reading the slab test)
 constexpr int kRoom = 4;   // free entries a visit needs (kernels.hip kDeferRoom)
 
 static int asInt(float f) { int i; std::memcpy(&i, &f, 4); return i; }
@@ -187,12 +192,62 @@ static Trace traverse(const BvhOutput &b, const Ray &r, bool any, int cap)
 	return T;
 }
 
+// The flat scan: one round, no visits
+static Trace traverseFlat(const BvhOutput &b, const FlatTable &ft, const Ray &r, bool any)
+{
+	Trace T;
+	float t_best = r.tmax;
+	int prim_best = -1;
+	const float t0 = any ? -1e-3f : r.tmin - 1e-3f * (1.f + std::fabs(r.tmin));
+	const float slack = r.tmax < 3.0e38f ? r.tmax * 1.0000005f + 1e-6f : 3.4e38f;
+	uint64_t m = 0;
+	const float od[3] = {r.o.x, r.o.y, r.o.z}, dd[3] = {r.d.x, r.d.y, r.d.z};
+	for(int i = 0; i < ft.n; ++i)
+	{
+		const FlatLeaf &l = ft.rec[i];
+		float lo = t0, hi = slack;
+		for(int a = 0; a < 3; ++a)
+		{
+			const float d = std::fabs(dd[a]) < 1e-20f ? std::copysign(1e-20f, dd[a]) : dd[a];
+			const float ta = (l.lo[a] - od[a]) / d, tb = (l.hi[a] - od[a]) / d;
+			lo = std::max(lo, std::min(ta, tb));
+			hi = std::min(hi, std::max(ta, tb));
+		}
+		if(lo <= hi) m |= ((uint64_t)l.bits_hi << 32) | l.bits_lo;
+	}
+	Round R{0, 0};
+	for(int q = 0; q < 64; ++q)
+	{
+		if(!((m >> q) & 1)) continue;
+		++R.tests;
+		const float *rec = &b.tris[12 * (size_t)q];
+		const float t = triTest(rec, r);
+		if(t == -1.f) continue;
+		const int prim = asInt(rec[7]);
+		if(any) { if(t < r.tmax && t >= 0.f) { t_best = t; prim_best = prim; break; } }
+		else if(t >= r.tmin && (t < t_best || (t == t_best && prim_best >= 0 && prim < prim_best))) { t_best = t; prim_best = prim; }
+	}
+	T.rounds.push_back(R);
+	T.tests = R.tests;
+	T.t = t_best;
+	T.prim = prim_best;
+	return T;
+}
+
 // VALU wave-instructions of one wave of rays and the trips of its triangle loops
 struct WaveCost { double valu = 0, trips = 0, iters = 0; };
-static WaveCost waveCost(const std::vector<Trace> &lanes, bool any, bool deferred)
+static WaveCost waveCost(const std::vector<Trace> &lanes, bool any, bool deferred, int flat_leaves = 0)
 {
 	WaveCost c;
 	c.valu = kSetup;
+	if(flat_leaves)
+	{
+		int tt = 0;
+		for(const Trace &t : lanes) tt = std::max(tt, t.tests);
+		c.trips = tt;
+		c.valu += (double)flat_leaves * kFlatBox + (double)tt * kTri;
+		return c;
+	}
 	const int order = any ? kOrderAny : kOrderClosest;
 	size_t rounds = 0;
 	for(const Trace &t : lanes) rounds = std::max(rounds, t.rounds.size());
@@ -212,7 +267,9 @@ int main()
 {
 	const Scene S = cornell();
 	const BvhOutput &b = S.bvh;
-	std::printf("Cornell: %d triangles, %d BVH4 nodes, largest leaf %d\n", (int)S.tris.size() / 3, b.n_nodes, b.max_leaf);
+	const FlatTable ft = buildFlatTable(b.nodes.data(), b.n_nodes);
+	std::printf("Cornell: %d triangles, %d BVH4 nodes, largest leaf %d, %d leaves (%d / %d / %d by mask word)\n", (int)S.tris.size() / 3, b.n_nodes,
+	            b.max_leaf, ft.n, ft.n_lo, ft.n_mid - ft.n_lo, ft.n - ft.n_mid);
 	std::mt19937 rng(11);
 	std::uniform_real_distribution<float> U(0.f, 1.f);
 	auto normalOf = [&](int prim) {
@@ -232,13 +289,14 @@ int main()
 			}
 	const std::vector<int> caps = {0, 4, 6, 8, 12, 16};
 	std::vector<double> total(caps.size(), 0.0);
+	double total_flat = 0, lists_box = 0, lists_waves = 0;   // lists_box: the cap-8 lists' box traversal (visits only)
 	std::printf("%-12s %6s %7s %7s |", "launch", "waves", "visits", "tests");
 	for(int cap : caps)
 	{
 		if(cap) std::printf("  cap %-2d valu trips |", cap);
 		else std::printf("  interleaved trips |");
 	}
-	std::printf("\n");
+	std::printf("  flat   valu trips |\n");
 	for(int it = 0; it < 4; ++it)
 	{
 		for(int kind = 0; kind < 2; ++kind)
@@ -273,6 +331,33 @@ int main()
 				}
 				total[c] += valu;
 				std::printf("  %11.0f %5.1f |", valu / waves, trips / waves);
+				if(caps[c] == 8)
+					for(size_t w = 0; w < waves; ++w)
+					{
+						const std::vector<Trace> lanes(tr[c].begin() + 64 * w, tr[c].begin() + std::min(Q.size(), 64 * (w + 1)));
+						lists_box += waveCost(lanes, any, true).iters * (kVisit + (any ? kOrderAny : kOrderClosest) + kAppend);
+						lists_waves += 1;
+					}
+			}
+			{
+				std::vector<Trace> fl;
+				for(size_t i = 0; i < Q.size(); ++i)
+				{
+					fl.push_back(traverseFlat(b, ft, Q[i], any));
+					const Trace &a = tr[0][i], &d = fl.back();
+					const bool same = any ? ((a.prim >= 0) == (d.prim >= 0)) : (a.prim == d.prim && (a.prim < 0 || a.t == d.t));
+					if(!same) { std::printf("MISMATCH it %d kind %d ray %zu flat: (%g %d) vs (%g %d)\n", it, kind, i, a.t, a.prim, d.t, d.prim); return 1; }
+				}
+				double valu = 0, trips = 0;
+				for(size_t w = 0; w < waves; ++w)
+				{
+					const std::vector<Trace> lanes(fl.begin() + 64 * w, fl.begin() + std::min(Q.size(), 64 * (w + 1)));
+					const WaveCost k = waveCost(lanes, any, false, ft.n);
+					valu += k.valu;
+					trips += k.trips;
+				}
+				total_flat += valu;
+				std::printf("  %11.0f %5.1f |", valu / waves, trips / waves);
 			}
 			std::printf("\n");
 		}
@@ -299,6 +384,8 @@ int main()
 	}
 	std::printf("whole mix (VALU summed over all waves, interleaved = 1):");
 	for(size_t c = 0; c < caps.size(); ++c) std::printf("  %s%d %.3f", caps[c] ? "cap " : "interleaved ", caps[c], total[c] / total[0]);
-	std::printf("\n");
+	std::printf("  flat %.3f\n", total_flat / total[0]);
+	std::printf("lists (cap 8): box traversal %.0f VALU per wave on the whole mix = %d VALU x %.1f leaf boxes\n", lists_box / lists_waves, kFlatBox,
+	            lists_box / lists_waves / kFlatBox);
 	return 0;
 }
