@@ -2,12 +2,67 @@
 // with an adaptive pass's pixel list), the lens functions, and cameraRay (the sample position of
 // TiledIntegrator::renderTile and PerspectiveCamera::shootRay).  Used by k_camera, the camera-stage k_shade and
 // k_path and k_gather's sample write (kernels.hip), k_done_flags (film.hip) and the render layers (layers.hip),
-// which regenerate the render's own camera rays bit for bit.  Device-inline code only.
+// which regenerate the render's own camera rays bit for bit.  Device-inline code only, but for the rays of the
+// orthographic, equirectangular and angular cameras at the top: those are YD functions of plain vectors and scalars,
+// which a host program compiles without the HIP headers (tests/camera_host.cc).
 #pragma once
 
-#include <hip/hip_runtime.h>
 #include <cstdint>
 #include "devmath.h"
+#include "camkind.h"
+
+namespace yafamd
+{
+
+// plane.h:37-40 with the camera's planes (normal cam_z): the ray's own from
+YD void cameraClip(V3 cam_z, V3 near_p, V3 far_p, V3 from, V3 dir, float &tmin, float &tmax)
+{
+	tmin = dot(cam_z, near_p - from) / dot(dir, cam_z);
+	tmax = dot(cam_z, far_p - from) / dot(dir, cam_z);
+}
+
+// camera_orthographic.cc:52-59: pos is pos_, vright / vup carry scale / res, the direction is cam_z as it stands
+YD void orthoRay(V3 pos, V3 vright, V3 vup, V3 vto, float px, float py, V3 &from, V3 &dir)
+{
+	from = pos + vright * px + vup * py;
+	dir = vto;
+}
+
+// camera_equirectangular.cc:48-60: phi and theta are long double products rounded to float; not normalised
+YD V3 equirectDir(V3 vright, V3 vup, V3 vto, int resx, int resy, float px, float py)
+{
+	const float u = 2.f * px / (float)resx - 1.f;
+	const float v = 2.f * py / (float)resy - 1.f;
+	const float phi = x87mul(kPi, u);
+	const float theta = x87mul(kDivPiBy2, v);
+	return fcos(theta) * (fcos(phi) * vto + fsin(phi) * vright) + fsin(theta) * vup;
+}
+
+// camera_angular.cc:58-78: false for a sample outside the circle (an invalid sample: no ray)
+YD bool angularDir(V3 vright, V3 vup, V3 vto, int resx, int resy, float aspect_ratio, float focal_length, float max_radius,
+                   int circular, int projection, float px, float py, V3 &dir)
+{
+	const float u = 1.f - 2.f * (px / (float)resx);
+	float v = 2.f * (py / (float)resy) - 1.f;
+	v *= aspect_ratio;
+	const float radius = sqrtf(u * u + v * v);
+	if(circular && radius > max_radius) return false;
+	float theta = 0.f;
+	if(!((u == 0.f) && (v == 0.f))) theta = libmAtan2f(v, u);
+	float phi;
+	if(projection == AP_ORTHOGRAPHIC) phi = mathAsin(radius / focal_length);
+	else if(projection == AP_STEREOGRAPHIC) phi = 2.f * libmAtanf(radius / (2.f * focal_length));
+	else if(projection == AP_EQUISOLID) phi = 2.f * mathAsin(radius / (2.f * focal_length));
+	else if(projection == AP_RECTILINEAR) phi = libmAtanf(radius / focal_length);
+	else phi = radius / focal_length;
+	dir = fsin(phi) * (fcos(theta) * vright + fsin(theta) * vup) + fcos(phi) * vto;
+	return true;
+}
+
+} // namespace yafamd
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #include "devscene.h"
 
 namespace yafamd
@@ -118,14 +173,12 @@ __device__ __forceinline__ SampleCoord sampleAt(const DevScene &S, const DevJob 
 	return sampleCoord(jobs, n_jobs, S.width, S.tile, S.spp, sid);
 }
 
-// One camera sample: TiledIntegrator::renderTile's sample position (integrator_tiled.cc:313-340) and
-// PerspectiveCamera::shootRay (camera_perspective.cc:128-146), plus the sample's Russian-roulette seed.
-// k_camera (wavefront) and k_path (megakernel) both start their samples here.
-__device__ __forceinline__ void cameraRay(const DevScene &S, const SampleCoord &sc, V3 &from, V3 &dir, float &tmin, float &tmax, uint32_t &seed)
+// The sample's position in camera pixels (integrator_tiled.cc:313-335; a cropped film starts at crop_x0 / crop_y0)
+// and the offset of its pixel's sampling sequences
+__device__ __forceinline__ void samplePos(const DevScene &S, const SampleCoord &sc, float &px, float &py, uint32_t &offset)
 {
-	// integrator_tiled.cc:313-335 (camera pixel coordinates: a cropped film starts at crop_x0 / crop_y0)
 	const int cx = sc.x + S.crop_x0, cy = sc.y + S.crop_y0;
-	const uint32_t offset = fnv32((uint32_t)cy * fnv32((uint32_t)cx));
+	offset = fnv32((uint32_t)cy * fnv32((uint32_t)cx));
 	const uint32_t sample_idx = S.base_offset + S.pass_offset + (uint32_t)sc.s;   // PixelSamplingData::sample_
 	float dx = 0.5f, dy = 0.5f;
 	if(S.aa_multipass)
@@ -139,7 +192,29 @@ __device__ __forceinline__ void cameraRay(const DevScene &S, const SampleCoord &
 		dx = (0.5f + (float)sc.s) * d_1;
 		dy = riLp((uint32_t)sc.s + offset);
 	}
-	const float px = (float)cx + dx, py = (float)cy + dy;
+	px = (float)cx + dx;
+	py = (float)cy + dy;
+}
+
+// RR generator: per-sample MWC (the reference seeds one per tile from rand(), so RR
+// output is matched statistically — integrator_tiled.cc:272), seeded from the pixel-major sample
+// id so that the image does not depend on how the film is split over GPUs or chunks
+// (64-bit id: W * H * spp passes 2^32 at 4K x 1024 spp; both halves are hashed)
+__device__ __forceinline__ uint32_t sampleSeed(const DevScene &S, const SampleCoord &sc)
+{
+	const uint64_t gid = ((uint64_t)sc.y * (uint64_t)S.width + (uint64_t)sc.x) * (uint64_t)S.spp + (uint64_t)sc.s;
+	const uint32_t gid32 = (uint32_t)gid ^ fnv32((uint32_t)(gid >> 32));
+	return fnv32(gid32 ^ S.rr_seed ^ (S.pass_offset * 0x9e3779b9u)) + 123u;
+}
+
+// One camera sample: TiledIntegrator::renderTile's sample position (integrator_tiled.cc:313-340) and
+// PerspectiveCamera::shootRay (camera_perspective.cc:128-146), plus the sample's Russian-roulette seed.
+// k_camera (wavefront) and k_path (megakernel) both start their samples here.
+__device__ __forceinline__ void cameraRay(const DevScene &S, const SampleCoord &sc, V3 &from, V3 &dir, float &tmin, float &tmax, uint32_t &seed)
+{
+	float px, py;
+	uint32_t offset;
+	samplePos(S, sc, px, py, offset);
 	// camera_perspective.cc:128-146, plane.h:37-40
 	const DevCamera &c = S.cam;
 	const V3 pos = v3(c.pos[0], c.pos[1], c.pos[2]);
@@ -161,13 +236,35 @@ __device__ __forceinline__ void cameraRay(const DevScene &S, const SampleCoord &
 		from = from + li;
 		dir = normalize(dir * c.dof_distance - li);
 	}
-	// RR generator: per-sample MWC (the reference seeds one per tile from rand(), so RR
-	// output is matched statistically — integrator_tiled.cc:272), seeded from the pixel-major sample
-	// id so that the image does not depend on how the film is split over GPUs or chunks
-	// (64-bit id: W * H * spp passes 2^32 at 4K x 1024 spp; both halves are hashed)
-	const uint64_t gid = ((uint64_t)sc.y * (uint64_t)S.width + (uint64_t)sc.x) * (uint64_t)S.spp + (uint64_t)sc.s;
-	const uint32_t gid32 = (uint32_t)gid ^ fnv32((uint32_t)(gid >> 32));
-	seed = fnv32(gid32 ^ S.rr_seed ^ (S.pass_offset * 0x9e3779b9u)) + 123u;
+	seed = sampleSeed(S, sc);
+}
+
+// shootRay of the orthographic, equirectangular and angular cameras (DevCamera::kind != CAM_PERSPECTIVE) at camera
+// pixel position (px, py): false for a sample the camera gives no ray (angular, outside the circle)
+__device__ __forceinline__ bool shootRayX(const DevCamera &c, float px, float py, V3 &from, V3 &dir, float &tmin, float &tmax)
+{
+	const V3 vright = v3(c.vright[0], c.vright[1], c.vright[2]), vup = v3(c.vup[0], c.vup[1], c.vup[2]), vto = v3(c.vto[0], c.vto[1], c.vto[2]);
+	from = v3(c.pos[0], c.pos[1], c.pos[2]);
+	bool valid = true;
+	if(c.kind == CAM_ORTHO) orthoRay(from, vright, vup, vto, px, py, from, dir);
+	else if(c.kind == CAM_EQUIRECT) dir = equirectDir(vright, vup, vto, c.resx, c.resy, px, py);
+	else valid = angularDir(vright, vup, vto, c.resx, c.resy, c.aspect_ratio, c.focal_length, c.max_radius, c.circular, c.projection, px, py, dir);
+	if(valid)
+		cameraClip(v3(c.cam_z[0], c.cam_z[1], c.cam_z[2]), v3(c.near_p[0], c.near_p[1], c.near_p[2]), v3(c.far_p[0], c.far_p[1], c.far_p[2]),
+		           from, dir, tmin, tmax);
+	return valid;
+}
+
+// cameraRay with those cameras: the CAMX instantiations of k_camera and k_layer_hits, launched for them alone.
+// These cameras have no lens, so no lens sample is drawn.
+__device__ __forceinline__ bool cameraRayX(const DevScene &S, const SampleCoord &sc, V3 &from, V3 &dir, float &tmin, float &tmax, uint32_t &seed)
+{
+	float px, py;
+	uint32_t offset;
+	samplePos(S, sc, px, py, offset);
+	seed = sampleSeed(S, sc);
+	return shootRayX(S.cam, px, py, from, dir, tmin, tmax);
 }
 
 } // namespace yafamd
+#endif // __HIPCC__

@@ -402,6 +402,46 @@ YD float libmAcosf(float x)
 	return 2.0f * (df + w);
 }
 
+// glibc's float asin (sysdeps/ieee754/flt-32 e_asinf.c: asin x = x + x^3 p(x^2) on |x| < 0.5, the acos-style
+// square-root form above), as AngularCamera::shootRay reaches it through math::asin
+YD float libmAsinf(float x)
+{
+	constexpr float pio2_hi = 1.57079637050628662109375f, pio2_lo = -4.37113900018624283e-8f, pio4_hi = 0.785398185253143310546875f;
+	constexpr float p0 = 1.666675248e-1f, p1 = 7.495297643e-2f, p2 = 4.547037598e-2f, p3 = 2.417951451e-2f, p4 = 4.216630880e-2f;
+	const int32_t hx = (int32_t)fbits(x), ix = hx & 0x7fffffff;
+	if(ix == 0x3f800000) return x * pio2_hi + x * pio2_lo;
+	if(ix > 0x3f800000) return (x - x) / (x - x);
+	if(ix < 0x3f000000)   // |x| < 0.5
+	{
+		if(ix < 0x32000000) return x;
+		const float t = x * x;
+		const float w = t * (p0 + t * (p1 + t * (p2 + t * (p3 + t * p4))));
+		return x + x * w;
+	}
+	const float t = (1.0f - fabsf(x)) * 0.5f;
+	const float p = t * (p0 + t * (p1 + t * (p2 + t * (p3 + t * p4))));
+	const float s = sqrtf(t);
+	float r;
+	if(ix >= 0x3F79999A) r = pio2_hi - (2.0f * (s + s * p) - pio2_lo);   // |x| > 0.975
+	else
+	{
+		const float w = bitsf(fbits(s) & 0xfffff000u);
+		const float c = (t - w * w) / (s + w);
+		const float pp = 2.0f * s * p - (pio2_lo - 2.0f * c);
+		const float q = pio4_hi - 2.0f * w;
+		r = pio4_hi - (pp - q);
+	}
+	return hx > 0 ? r : -r;
+}
+
+// math::asin (math.h:260-266): the range limit instead of a NaN outside [-1, 1]
+YD float mathAsin(float x)
+{
+	if(x <= -1.f) return -kDivPiBy2F;
+	else if(x >= 1.f) return kDivPiBy2F;
+	return libmAsinf(x);
+}
+
 // x > C / x < -C with C long double (exact for float x, see DESIGN.md numerics note)
 YD bool gtC(float x, const X87Const &c) { return (double)x > c.hi || ((double)x == c.hi && c.lo < 0.0); }
 YD bool ltNegC(float x, const X87Const &c) { return (double)x < -c.hi || ((double)x == -c.hi && c.lo < 0.0); }

@@ -12,6 +12,7 @@
 #pragma once
 #include <cstdint>
 #include <hip/hip_runtime.h>
+#include "camkind.h"
 
 namespace yafamd
 {
@@ -197,6 +198,14 @@ struct DevCamera
 	float aperture, dof_distance;
 	int bokeh_type, bokeh_bias;    // BokehType (0 disk1, 1 disk2, 3..6 polygon, 7 ring), BkhBiasType
 	float ls[16];                  // polygon vertices (cos, sin) pairs
+	// the other cameras (camera.h cameraRayX; the CAMX instantiations of k_camera and the layers' kernels).  kind
+	// CAM_PERSPECTIVE also serves the architect camera, which differs in the host's vup alone.  Orthographic: pos is
+	// pos_ and vright / vup carry scale / res; angular: vright is negated when mirrored
+	int kind;                      // CameraKind
+	int projection;                // AngularProjection
+	int circular;                  // angular: a sample with radius > max_radius has no ray (an invalid sample)
+	float focal_length, max_radius, aspect_ratio;   // AngularCamera's focal_length_, max_radius_, Camera's aspect_ratio_
+	int pad2[2];
 };
 
 // A band of pixel rows rendered as a run of tiles (imagesplitter.cc:30-49 linear order):

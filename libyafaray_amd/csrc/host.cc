@@ -1085,8 +1085,23 @@ bool Scene::createCamera(const std::string &name, const ParamMap &p)
 {
 	std::string type;
 	p.get("type", type);
-	if(type != "perspective") { log.error("Scene: camera type '" + type + "' is not supported by the GPU core"); return false; }
+	// Camera::factory (camera.cc:43-47)
+	if(type != "perspective" && type != "architect" && type != "orthographic" && type != "equirectangular" && type != "angular")
+	{
+		log.error("Scene: camera type '" + type + "' is not supported by the GPU core");
+		return false;
+	}
 	CameraDesc c;
+	c.type = type;
+	// camera_angular.cc:82-88, camera_equirectangular.cc:64-67 (the other three: -1)
+	if(type == "angular" || type == "equirectangular") c.far_clip = -1.0e38f;
+	p.get("scale", c.scale);
+	p.get("angle", c.angle);
+	c.max_angle = c.angle;
+	p.get("max_angle", c.max_angle);
+	p.get("circular", c.circular);
+	p.get("mirrored", c.mirrored);
+	p.get("projection", c.projection);
 	p.getVec("from", c.from);
 	p.getVec("to", c.to);
 	p.getVec("up", c.up);
@@ -1912,10 +1927,50 @@ bool Scene::render(const Callbacks &cb, yafaray_ProgressBarCallback_t progress, 
 		cam_y = nrm(cam_y);
 		cam_z = nrm(cam_z);
 		F3 vright = cam_x, vup = mul(cam_y, aspect_ratio);
-		const F3 vto = sub(mul(cam_z, c.focal), mul(add(vup, vright), static_cast<float>(0.5)));
+		// camera_architect.cc:55-65: the image plane's vertical is the world's -z; dof_rt / dof_up keep the camera axes
+		if(c.type == "architect") vup = mul(F3{0.f, 0.f, -1.f}, aspect_ratio);
+		F3 vto = sub(mul(cam_z, c.focal), mul(add(vup, vright), static_cast<float>(0.5)));
 		vup = {vup.x / (float)c.resy, vup.y / (float)c.resy, vup.z / (float)c.resy};
 		vright = {vright.x / (float)c.resx, vright.y / (float)c.resx, vright.z / (float)c.resx};
-		put(S.cam.pos, pos);
+		F3 ray_pos = pos;
+		S.cam.kind = CAM_PERSPECTIVE;
+		S.cam.aspect_ratio = aspect_ratio;
+		if(c.type == "orthographic")
+		{
+			// camera_orthographic.cc:36-50
+			S.cam.kind = CAM_ORTHO;
+			vright = cam_x;
+			vup = mul(cam_y, aspect_ratio);
+			vto = cam_z;
+			ray_pos = sub(pos, mul(add(vup, vright), static_cast<float>(0.5 * c.scale)));
+			vup = mul(vup, c.scale / (float)c.resy);
+			vright = mul(vright, c.scale / (float)c.resx);
+		}
+		else if(c.type == "equirectangular" || c.type == "angular")
+		{
+			// camera_equirectangular.cc:37-46, camera_angular.cc:30-56, 113-114
+			S.cam.kind = c.type == "angular" ? CAM_ANGULAR : CAM_EQUIRECT;
+			vright = cam_x;
+			vup = cam_y;
+			vto = cam_z;
+		}
+		if(S.cam.kind == CAM_ANGULAR)
+		{
+			// the factory's long double products, rounded to the constructor's float parameters
+			const float angle = static_cast<float>(c.angle * hm::div_pi_by_180), max_angle = static_cast<float>(c.max_angle * hm::div_pi_by_180);
+			S.cam.max_radius = max_angle / angle;
+			S.cam.circular = c.circular ? 1 : 0;
+			S.cam.projection = c.projection == "orthographic" ? AP_ORTHOGRAPHIC : c.projection == "stereographic" ? AP_STEREOGRAPHIC
+			                   : c.projection == "equisolid_angle" ? AP_EQUISOLID : c.projection == "rectilinear" ? AP_RECTILINEAR : AP_EQUIDISTANT;
+			// (std::tan on a float: the host libm's tanf, the one value of a camera that comes from it)
+			if(S.cam.projection == AP_ORTHOGRAPHIC) S.cam.focal_length = 1.f / hm::sinf_fast(angle);
+			else if(S.cam.projection == AP_STEREOGRAPHIC) S.cam.focal_length = 1.f / 2.f / std::tan(angle / 2.f);
+			else if(S.cam.projection == AP_EQUISOLID) S.cam.focal_length = 1.f / 2.f / hm::sinf_fast(angle / 2.f);
+			else if(S.cam.projection == AP_RECTILINEAR) S.cam.focal_length = 1.f / std::tan(angle);
+			else S.cam.focal_length = 1.f / angle;
+			if(c.mirrored) vright = mul(vright, static_cast<float>(-1.0));
+		}
+		put(S.cam.pos, ray_pos);
 		put(S.cam.vright, vright);
 		put(S.cam.vup, vup);
 		put(S.cam.vto, vto);
@@ -1930,6 +1985,9 @@ bool Scene::render(const Callbacks &cb, yafaray_ProgressBarCallback_t progress, 
 			const bool near0 = dn.x == 0.f && dn.y == 0.f && dn.z == 0.f;
 			const float far_num = cam_z.x * df.x + cam_z.y * df.y + cam_z.z * df.z;
 			S.cam.ray_tt = (near0 && far_num < -1e-20f) ? 0 : 1;
+			// the other cameras' rays keep their own range: an orthographic ray does not start at the position, and
+			// a ray that points away from cam_z turns the far plane's negative numerator into a positive tmax
+			if(S.cam.kind != CAM_PERSPECTIVE) S.cam.ray_tt = 1;
 		}
 		S.cam.resx = c.resx;
 		S.cam.resy = c.resy;

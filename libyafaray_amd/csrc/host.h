@@ -142,6 +142,13 @@ struct CameraDesc
 	float near_clip = 0.f, far_clip = -1.f;
 	float dof_distance = 0.f, bokeh_rotation = 0.f;
 	std::string bokeh_type = "disk1", bokeh_bias = "uniform";
+	// perspective, architect, orthographic, equirectangular or angular (camera.cc:43-47); each factory's own
+	// defaults are set by Scene::createCamera (farClip of the last two: -1.0e38f)
+	std::string type = "perspective";
+	float scale = 1.f;                               // orthographic
+	double angle = 90.0, max_angle = 90.0;           // angular, degrees
+	bool circular = true, mirrored = false;
+	std::string projection;                          // angular: equidistant unless one of the four other names
 };
 
 struct RenderSetup

@@ -304,6 +304,12 @@ __device__ unsigned long long g_phase[16];
 // ---------------------------------------------------------------------------------------------
 // k_camera (sampleAt, cameraRay: camera.h)
 // ---------------------------------------------------------------------------------------------
+// CAMX: the orthographic, equirectangular and angular cameras (cameraRayX), launched for them alone and timed as
+// "k_camera_xc".  A sample the camera gives no ray (angular, outside the circle: an invalid sample,
+// integrator_tiled.cc:342-347) keeps its queue entry, so the segment counts and the camera-stage k_shade's inverse
+// dealing stand: its ray is the "no ray" marker (a NaN direction, which k_trace and k_surface skip) and its hit
+// record a miss, which the camera stage of k_shade finalises as the film's default colour (black, alpha 1).
+template<bool CAMX = false>
 __global__ void __launch_bounds__(256) k_camera(DevScene S, DevPaths P, DevQueues Q, DevCounters cnt,
                                                  const DevJob *jobs, int n_jobs, uint64_t chunk_base, int n, int write_pr)
 {
@@ -324,7 +330,16 @@ __global__ void __launch_bounds__(256) k_camera(DevScene S, DevPaths P, DevQueue
 	V3 from, dir;
 	float tmin, tmax;
 	uint32_t seed;
-	cameraRay(S, sc, from, dir, tmin, tmax, seed);
+	if constexpr(CAMX)
+	{
+		if(!cameraRayX(S, sc, from, dir, tmin, tmax, seed))
+		{
+			dir = v3(__builtin_nanf(""), 0.f, 0.f);
+			tmin = tmax = 0.f;
+			Q.hit_prim[a] = -1;
+		}
+	}
+	else cameraRay(S, sc, from, dir, tmin, tmax, seed);
 	// the compact record carries the sample id and the stage in pr (offset / sample index derive
 	// from the sample id); a specular recursion tree keeps them in the queue's slot and col.w
 	// (compact record: the zero throughput, path colour, w and flags of a camera entry are implied by
@@ -2131,8 +2146,19 @@ k_shade(ShadeArgs A)
 					// integrator_tiled.cc:707-720 background
 					C3 bg = c3(0.f);
 					float a = 1.f;
-					if(S.bg_transp && (!EXT || S.cur_level == 0 || S.bg_transp_refract)) a = 0.f;
-					else if(S.has_bg) bg = C3{S.bg[0], S.bg[1], S.bg[2]};
+					// a sample the angular camera gave no ray (k_camera's CAMX form left the "no ray" marker in its
+					// place): integrator_tiled.cc:342-347 adds the layers' default colour, black with alpha 1
+					bool no_ray = false;
+					if(S.cam.circular && S.cur_level == 0)
+					{
+						const float ddx = A.Q.ray_d[3 * (size_t)i];
+						no_ray = ddx != ddx;
+					}
+					if(!no_ray)
+					{
+						if(S.bg_transp && (!EXT || S.cur_level == 0 || S.bg_transp_refract)) a = 0.f;
+						else if(S.has_bg) bg = C3{S.bg[0], S.bg[1], S.bg[2]};
+					}
 					if(EXT && S.tree)
 					{
 						S.node_own[sid] = f4(bg, a);
@@ -5993,7 +6019,10 @@ hipError_t yafamd_launch_camera(const DevScene *S, const DevPaths *P, const DevQ
 	// which reads no pr record
 	if(n <= 0) return hipSuccess;
 	const int threads = max(n, (int)S->n_seg);   // the first n_seg threads also write the segment counts
-	hipLaunchKernelGGL(k_camera, dim3((threads + 255) / 256), dim3(256), 0, st, *S, *P, *Q, *cnt, jobs, n_jobs, chunk_base, n, write_pr);
+	// (CAMX: the orthographic, equirectangular and angular cameras; the caller times it as k_camera_xc)
+	if(S->cam.kind != CAM_PERSPECTIVE)
+		hipLaunchKernelGGL((k_camera<true>), dim3((threads + 255) / 256), dim3(256), 0, st, *S, *P, *Q, *cnt, jobs, n_jobs, chunk_base, n, write_pr);
+	else hipLaunchKernelGGL((k_camera<false>), dim3((threads + 255) / 256), dim3(256), 0, st, *S, *P, *Q, *cnt, jobs, n_jobs, chunk_base, n, write_pr);
 	return hipGetLastError();
 }
 
@@ -6274,7 +6303,8 @@ hipError_t yafamd_launch_tshadow(const DevScene *S, const DevQueues *Q, const De
 // hipErrorInvalidValue when the scene is not eligible (yafamd_path_eligible).
 int yafamd_path_eligible(const DevScene *S, int stack_depth, int spill)
 {
-	return (kExperiments && !S->has_ext_light && !S->ext && !S->tree && !S->tr_shad && !S->has_attr && !S->do_ao && !S->gather_on && !S->caus_map && S->integrator != INT_PHOTON &&
+	// (k_path calls the perspective cameraRay alone: the other cameras render through the wavefront)
+	return (kExperiments && S->cam.kind == CAM_PERSPECTIVE && !S->has_ext_light && !S->ext && !S->tree && !S->tr_shad && !S->has_attr && !S->do_ao && !S->gather_on && !S->caus_map && S->integrator != INT_PHOTON &&
 	        S->scene_in_lds && S->node_f4 == 8 && !spill && S->small_tables && S->nee_k >= 1 && S->nee_k <= kPathMaxK && !S->brute &&
 	        pathLdsBytes(*S, stack_depth) <= 64 * 1024)
 	           ? 1

@@ -51,7 +51,9 @@ __device__ __forceinline__ bool layerClosest(const DevScene &S, float4 *smem, in
 // min_depth_ = the smallest non-negative one (a miss keeps the camera's tmax).  Non-negative floats
 // order like their bits, so the wave's extremes go to two integer atomics.  range: (min, max) bits,
 // started at (1e38f, 0.f).
-template<bool WIDE>
+// CAMX: the orthographic, equirectangular and angular cameras (camera.h shootRayX).  The reference takes no notice of
+// a ray the camera did not set up, so the render refuses the circular angular camera before this pass (render.cc).
+template<bool WIDE, bool CAMX = false>
 __global__ void __launch_bounds__(kTraceBlock) k_layer_depth(DevScene S, uint32_t *range, int stack_depth)
 {
 	extern __shared__ float4 smem[];
@@ -62,26 +64,37 @@ __global__ void __launch_bounds__(kTraceBlock) k_layer_depth(DevScene S, uint32_
 	if(k < w * h)
 	{
 		const float px = (float)(k / w), py = (float)(k % w);
-		const V3 pos = v3(c.pos[0], c.pos[1], c.pos[2]);
-		V3 dir = v3(c.vright[0], c.vright[1], c.vright[2]) * px + v3(c.vup[0], c.vup[1], c.vup[2]) * py + v3(c.vto[0], c.vto[1], c.vto[2]);
-		dir = normalize(dir);
-		const V3 cz = v3(c.cam_z[0], c.cam_z[1], c.cam_z[2]);
-		const float tmin = dot(cz, v3(c.near_p[0], c.near_p[1], c.near_p[2]) - pos) / dot(dir, cz);
-		const float tmax = dot(cz, v3(c.far_p[0], c.far_p[1], c.far_p[2]) - pos) / dot(dir, cz);
-		V3 from = pos;
-		if(c.aperture != 0.f)
+		V3 from, dir;
+		float tmin, tmax;
+		bool valid = true;
+		if constexpr(CAMX) valid = shootRayX(c, px, py, from, dir, tmin, tmax);
+		else
 		{
-			float u, v;
-			lensUv(c, 0.5f, 0.5f, u, v);
-			const V3 li = v3(c.dof_rt[0], c.dof_rt[1], c.dof_rt[2]) * u + v3(c.dof_up[0], c.dof_up[1], c.dof_up[2]) * v;
-			from = from + li;
-			dir = normalize(dir * c.dof_distance - li);
+			const V3 pos = v3(c.pos[0], c.pos[1], c.pos[2]);
+			dir = v3(c.vright[0], c.vright[1], c.vright[2]) * px + v3(c.vup[0], c.vup[1], c.vup[2]) * py + v3(c.vto[0], c.vto[1], c.vto[2]);
+			dir = normalize(dir);
+			const V3 cz = v3(c.cam_z[0], c.cam_z[1], c.cam_z[2]);
+			tmin = dot(cz, v3(c.near_p[0], c.near_p[1], c.near_p[2]) - pos) / dot(dir, cz);
+			tmax = dot(cz, v3(c.far_p[0], c.far_p[1], c.far_p[2]) - pos) / dot(dir, cz);
+			from = pos;
+			if(c.aperture != 0.f)
+			{
+				float u, v;
+				lensUv(c, 0.5f, 0.5f, u, v);
+				const V3 li = v3(c.dof_rt[0], c.dof_rt[1], c.dof_rt[2]) * u + v3(c.dof_up[0], c.dof_up[1], c.dof_up[2]) * v;
+				from = from + li;
+				dir = normalize(dir * c.dof_distance - li);
+			}
 		}
-		float t;
-		int prim;
-		const bool hit = layerClosest<WIDE>(S, smem, stack_depth, from, dir, c.ray_tt ? tmin : 0.f,
-		                                    (c.ray_tt && tmax >= 0.f) ? tmax : __builtin_huge_valf(), t, prim);
-		tm = hit ? t : tmax;
+		// (CAMX: a pixel without a ray takes no part; the render refuses such a camera before this pass)
+		if(valid)
+		{
+			float t;
+			int prim;
+			const bool hit = layerClosest<WIDE>(S, smem, stack_depth, from, dir, c.ray_tt ? tmin : 0.f,
+			                                    (c.ray_tt && tmax >= 0.f) ? tmax : __builtin_huge_valf(), t, prim);
+			tm = hit ? t : tmax;
+		}
 	}
 	// (tmax > max_depth_ with max_depth_ >= 0; tmax < min_depth_ && tmax >= 0: a NaN takes part in neither)
 	uint32_t hi = (tm > 0.f) ? __float_as_uint(tm) : 0u;
@@ -107,6 +120,7 @@ __global__ void k_layer_depth_fin(float *range)
 // ---------------------------------------------------------------------------------------------
 // first hits
 // ---------------------------------------------------------------------------------------------
+constexpr int kLayerNoRay = -2;   // the record's primitive of a sample the camera gave no ray (-1: a miss)
 // material_shiny_diffuse.cc:662-666 getDiffuseColor (every other material: Material's black)
 __device__ __forceinline__ C3 layerDiffuseColor(const DevScene &S, int prim, V3 o, V3 d, float t)
 {
@@ -124,7 +138,8 @@ __device__ __forceinline__ C3 layerDiffuseColor(const DevScene &S, int prim, V3 
 	return C3{k * dcol.r, k * dcol.g, k * dcol.b};
 }
 
-template<bool WIDE>
+// CAMX: the cameras of cameraRayX; a sample without a ray leaves the record (-1, kLayerNoRay): every layer's default colour
+template<bool WIDE, bool CAMX = false>
 __global__ void __launch_bounds__(kTraceBlock) k_layer_hits(DevScene S, DevLayers L, const DevJob *jobs, int n_jobs, uint64_t chunk_base, int n,
                                                             int stack_depth)
 {
@@ -135,7 +150,17 @@ __global__ void __launch_bounds__(kTraceBlock) k_layer_hits(DevScene S, DevLayer
 	V3 from, dir;
 	float tmin, tmax;
 	uint32_t seed;
-	cameraRay(S, sc, from, dir, tmin, tmax, seed);
+	if constexpr(CAMX)
+	{
+		if(!cameraRayX(S, sc, from, dir, tmin, tmax, seed))
+		{
+			const size_t at = ((size_t)sc.y * S.width + sc.x) * S.spp + sc.s;
+			L.rec[at] = make_float4(-1.f, __int_as_float(kLayerNoRay), 0.f, 0.f);
+			if(L.albedo) L.albedo[at] = make_float4(0.f, 0.f, 0.f, 1.f);
+			return;
+		}
+	}
+	else cameraRay(S, sc, from, dir, tmin, tmax, seed);
 	// (k_camera / k_trace: without ray_tt every camera ray has (0, unbounded))
 	float t;
 	int prim;
@@ -177,6 +202,7 @@ __device__ __forceinline__ float4 layerValue(int kind, const DevLayers &L, const
 	const int prim = __float_as_int(rec.y);
 	if(kind == LK_ZDEPTH_ABS || kind == LK_ZDEPTH_NORM || kind == LK_MIST)
 	{
+		if(prim == kLayerNoRay) return make_float4(0.f, 0.f, 0.f, 1.f);   // no camera ray: LayerDef's default colour
 		if(t < 0.f) return make_float4(0.f, 0.f, 0.f, 0.f);   // background: fully transparent
 		if(kind == LK_ZDEPTH_ABS) return layerGray(t);
 		const float mn = L.depth[0], mx = L.depth[1];
@@ -357,7 +383,10 @@ hipError_t yafamd_layer_depth_range(const DevScene *S, float *range, int stack_d
 	{
 		const size_t stack_bytes = (size_t)stack_depth * kTraceBlock * sizeof(int);
 		const dim3 grid((n + kTraceBlock - 1) / kTraceBlock);
-		if(S->node_f4 == 8) hipLaunchKernelGGL((k_layer_depth<true>), grid, dim3(kTraceBlock), stack_bytes, st, *S, (uint32_t *)range, stack_depth);
+		const bool camx = S->cam.kind != CAM_PERSPECTIVE;
+		if(camx && S->node_f4 == 8) hipLaunchKernelGGL((k_layer_depth<true, true>), grid, dim3(kTraceBlock), stack_bytes, st, *S, (uint32_t *)range, stack_depth);
+		else if(camx) hipLaunchKernelGGL((k_layer_depth<false, true>), grid, dim3(kTraceBlock), stack_bytes, st, *S, (uint32_t *)range, stack_depth);
+		else if(S->node_f4 == 8) hipLaunchKernelGGL((k_layer_depth<true>), grid, dim3(kTraceBlock), stack_bytes, st, *S, (uint32_t *)range, stack_depth);
 		else hipLaunchKernelGGL((k_layer_depth<false>), grid, dim3(kTraceBlock), stack_bytes, st, *S, (uint32_t *)range, stack_depth);
 		e = hipGetLastError();
 		if(e != hipSuccess) return e;
@@ -372,7 +401,10 @@ hipError_t yafamd_launch_layer_hits(const DevScene *S, const DevLayers *L, const
 	if(n <= 0) return hipSuccess;
 	const size_t stack_bytes = (size_t)stack_depth * kTraceBlock * sizeof(int);
 	const dim3 grid((n + kTraceBlock - 1) / kTraceBlock);
-	if(S->node_f4 == 8) hipLaunchKernelGGL((k_layer_hits<true>), grid, dim3(kTraceBlock), stack_bytes, st, *S, *L, jobs, n_jobs, chunk_base, n, stack_depth);
+	const bool camx = S->cam.kind != CAM_PERSPECTIVE;
+	if(camx && S->node_f4 == 8) hipLaunchKernelGGL((k_layer_hits<true, true>), grid, dim3(kTraceBlock), stack_bytes, st, *S, *L, jobs, n_jobs, chunk_base, n, stack_depth);
+	else if(camx) hipLaunchKernelGGL((k_layer_hits<false, true>), grid, dim3(kTraceBlock), stack_bytes, st, *S, *L, jobs, n_jobs, chunk_base, n, stack_depth);
+	else if(S->node_f4 == 8) hipLaunchKernelGGL((k_layer_hits<true>), grid, dim3(kTraceBlock), stack_bytes, st, *S, *L, jobs, n_jobs, chunk_base, n, stack_depth);
 	else hipLaunchKernelGGL((k_layer_hits<false>), grid, dim3(kTraceBlock), stack_bytes, st, *S, *L, jobs, n_jobs, chunk_base, n, stack_depth);
 	return hipGetLastError();
 }

@@ -2218,6 +2218,14 @@ bool GpuRenderer::Run::setupLayers()
 			}
 			else
 			{
+				// precalcDepths intersects the ray of every pixel, also where shootRay set none up (outside the circle
+				// the reference reads a default-constructed ray): nothing to be faithful to
+				if(S.cam.kind == CAM_ANGULAR && S.cam.circular)
+				{
+					log_.error("Render: an angular camera with circular = true cannot be combined with a normalised depth (z-depth-norm) or mist layer, "
+					           "whose depth range is taken over every pixel's ray; set circular = false or a farClip");
+					return false;
+				}
 				PROF(KK_LAYER_HITS, yafamd_layer_depth_range(&S, (float *)d.lay_depth.p, d.stack_depth, d.stream));
 				layer_rays += (uint64_t)std::max(0, S.cam.resx) * (uint64_t)std::max(0, S.cam.resy);
 			}
@@ -2807,7 +2815,7 @@ bool GpuRenderer::Run::runSamples(uint64_t n_total)
 		}
 		if(S.tree) HIPCHECK(hipMemsetAsync(d.spawn_count.p, 0, 16, d.stream));
 		S.cur_level = 0;
-		PROF(KK_CAMERA, yafamd_launch_camera(&S, &d.P[0], &d.Q[0], &cnt[0], (const DevJob *)d.jobs.p, n_jobs, base, n, sch.shade_stages ? 0 : 1, d.stream));
+		PROF(S.cam.kind != CAM_PERSPECTIVE ? KK_CAMERA_XC : KK_CAMERA, yafamd_launch_camera(&S, &d.P[0], &d.Q[0], &cnt[0], (const DevJob *)d.jobs.p, n_jobs, base, n, sch.shade_stages ? 0 : 1, d.stream));
 		if(!iterate(base)) return false;
 		if(S.tree && !runTreeLevels(base, n)) return false;
 	}
@@ -3341,7 +3349,7 @@ bool GpuRenderer::Run::finish()
 			ktimes_.ms[pr.kind] += t;
 			++ktimes_.launches[pr.kind];
 		}
-		ktimes_.items[KK_CAMERA] = samples_total;
+		ktimes_.items[S.cam.kind != CAM_PERSPECTIVE ? KK_CAMERA_XC : KK_CAMERA] = samples_total;
 		ktimes_.items[KK_FILM] = samples_total;
 		ktimes_.items[KK_LAYER_HITS] = layer_rays;
 		ktimes_.items[KK_LAYER_FILM] = n_lay > 0 ? samples_total : 0;

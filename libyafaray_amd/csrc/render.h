@@ -107,6 +107,7 @@ enum KernelKind : int
 	KK_LAYER_HITS, KK_LAYER_FILM,
 	KK_SHADE_STAGED,   // launches only: the k_shade launches (counted and timed under KK_SHADE) that were stage-specialised
 	KK_LIGHTS_XL,      // launches only: the k_nee / k_dfr / k_photon_emit / k_fg launches that ran an XL instantiation (lights_ext.h)
+	KK_CAMERA_XC,      // k_camera's CAMX instantiation: the orthographic, equirectangular and angular cameras (no KK_CAMERA launch then)
 	KK_COUNT
 };
 inline const char *kernelKindName(int k)
@@ -114,7 +115,7 @@ inline const char *kernelKindName(int k)
 	static const char *n[KK_COUNT] = {"k_camera", "k_trace", "k_surface", "k_tshadow", "k_shade", "k_nee", "k_gather", "k_spawn",
 	                                  "k_combine", "k_film", "aa_next_pass", "k_photon_emit", "k_photon_bounce", "photon_compact",
 	                                  "pkd_build", "k_fg", "k_pregather", "k_gather_walk", "k_path", "k_dfr", "k_layer_hits", "k_layer_film",
-	                                  "k_shade_staged", "k_lights_xl"};
+	                                  "k_shade_staged", "k_lights_xl", "k_camera_xc"};
 	return (k >= 0 && k < KK_COUNT) ? n[k] : "";
 }
 struct KernelTimes

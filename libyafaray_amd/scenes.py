@@ -101,6 +101,9 @@ class Light:
     angle: float = 0.27
 
 
+CAMERA_TYPES = ("perspective", "architect", "orthographic", "equirectangular", "angular")
+
+
 @dataclass
 class Camera:
     from_: tuple
@@ -118,6 +121,16 @@ class Camera:
     bokeh_type: str = "disk1"       # disk1 disk2 triangle square pentagon hexagon ring
     bokeh_bias: str = "uniform"     # uniform center edge
     bokeh_rotation: float = 0.0
+    # camera.cc:43-47: perspective, architect (focal, depth of field as perspective), orthographic (scale),
+    # equirectangular, angular.  far_clip left at -1.0 means the type's own default: -1 for the first three and
+    # -1.0e38 for angular and equirectangular, whose rays also point away from the view direction
+    type: str = "perspective"
+    scale: float = 1.0              # orthographic: the width of the view in scene units
+    angle: float = 90.0             # angular: half the field of view at radius 1, degrees
+    max_angle: float = None         # angular: the circle's edge (None: angle)
+    circular: bool = True           # angular: no rays outside the circle (the film's default colour there)
+    mirrored: bool = False          # angular
+    projection: str = "equidistant"  # angular: equidistant orthographic stereographic equisolid_angle rectilinear
 
 
 @dataclass
@@ -663,17 +676,31 @@ def apply(spec: SceneSpec, api) -> None:
             raise RuntimeError("addInstance('%s') failed: %s" % (base, api.last_error()))
     cam = spec.camera
     api.paramsClearAll()
-    api.paramsSetString("type", "perspective")
+    if cam.type not in CAMERA_TYPES:
+        raise ValueError("camera type '%s': one of %s" % (cam.type, ", ".join(CAMERA_TYPES)))
+    api.paramsSetString("type", cam.type)
     api.paramsSetVector("from", *cam.from_)
     api.paramsSetVector("to", *cam.to)
     api.paramsSetVector("up", *cam.up)
     api.paramsSetInt("resx", cam.resx)
     api.paramsSetInt("resy", cam.resy)
-    api.paramsSetFloat("focal", cam.focal)
+    lens = cam.type in ("perspective", "architect")
+    if lens:
+        api.paramsSetFloat("focal", cam.focal)
     api.paramsSetFloat("aspect_ratio", cam.aspect_ratio)
     api.paramsSetFloat("nearClip", cam.near_clip)
-    api.paramsSetFloat("farClip", cam.far_clip)
-    if cam.aperture != 0.0:
+    if cam.far_clip != -1.0 or cam.type not in ("angular", "equirectangular"):
+        api.paramsSetFloat("farClip", cam.far_clip)
+    if cam.type == "orthographic":
+        api.paramsSetFloat("scale", cam.scale)
+    if cam.type == "angular":
+        api.paramsSetFloat("angle", cam.angle)
+        if cam.max_angle is not None:
+            api.paramsSetFloat("max_angle", cam.max_angle)
+        api.paramsSetBool("circular", cam.circular)
+        api.paramsSetBool("mirrored", cam.mirrored)
+        api.paramsSetString("projection", cam.projection)
+    if lens and cam.aperture != 0.0:
         api.paramsSetFloat("aperture", cam.aperture)
         api.paramsSetFloat("dof_distance", cam.dof_distance)
         api.paramsSetString("bokeh_type", cam.bokeh_type)
