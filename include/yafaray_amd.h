@@ -117,6 +117,41 @@ YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_traceQueued(yafaray_Interface_t 
  * and reuse its thinning scratch from call to call. */
 YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_thinRadPoints(yafaray_Interface_t *interface, const float *pos, const float *nrm, int n,
                                                               float maxrad, int mode, unsigned int *kept, int *n_kept, int *rounds);
+/* Test infrastructure (LIBYAFARAY_AMD_1.11): the photon-map queries of a render on a caller-supplied map.
+ * pos (and dir, for the nearest kinds): n x 3 floats; queries (and normals, nearest kinds): m x 3 floats.  The point
+ * kd-tree is built by the production builder (YAFARAY_AMD_PKD_ORDER applies as in a render); every photon index
+ * that comes back is an index into pos.  The m points become gather requests dealt over n_seg queue segments with
+ * ragged counts (segment 0 empty when n_seg > 1) and run through the launches a render makes.  kind:
+ *   0  what a render of this map would choose (k, YAFARAY_AMD_GATHER / _GATHER_HEAP / _GATHER_WALK / _GATHER_LOG);
+ *      counters[7] names the path taken (1, 3, 4 or 5)
+ *   1  the one-pass k_gather lookup            2  k_pregather's lookup
+ *   3  k_gather_walk + packed-heap replay      4  k_gather_walk + split-heap replay (k <= 64 for both)
+ *   5  the bounded walk + packed-heap replay (experiments builds only; where kind 0 takes this walk it replays with
+ *      the heap a render would, the split one by default)
+ *   6  pkNearest    7  the radiance grid (gridNearest; -2 = tie -> the kd search, as final gathering does)
+ *   8  pkNearestLds (log_cap > 0: that many LDS stack levels instead of depth + 1; at most 32)
+ * Gather kinds (0 - 5) search k photons within the squared radius radius2 and return per query: found, the final
+ * squared radius, and the heap as the density estimate reads it, in heap-array order: heap_idx / heap_dist hold
+ * k slots per query, the first found[q] set (the others 0xffffffff / 0).  log_cap: the walk's log entries per
+ * request (even, >= k; 0 = a render's: max(k, YAFARAY_AMD_GATHER_LOG or 512) rounded up to even); a request that
+ * accepts more overflows and is looked up again (counters[2]).  log_n (m) and log_e (m x log cap x 2 words: photon,
+ * squared distance bits), both optional, receive the walk's raw log of kinds 0 and 3 - 5: log_n[q] entries were
+ * accepted, the first min(log_n[q], cap) of them stored.
+ * Nearest kinds search within radius2 for the nearest photon whose dir faces the query's normal (dot > 0):
+ * nearest[q] = its index, -1 none.  Kind 7 also fills grid_raw (m) with gridNearest's own answer, -2 where it saw a
+ * tie or no grid could be built (counters[10] = 0), and nearest holds the answer after the kd search settled those.
+ * counters (16 values): 0 kd nodes visited, 1 photons the walk accepted, 2 requests whose log overflowed, 3 the
+ * tree's deepest level (root 0), 4 pm_stack (depth + 1), 5 the stack levels kept in LDS (walk kinds, kind 8),
+ * 6 whether the walk got a spill column for deeper levels, 7 the path, 8 the largest n_seg allowed, 9 the log cap
+ * used, 10 whether the grid was built, 11 queries the grid answered -2, 12 photons found in all, 13 whether the
+ * leaves are in kd order.  False with a lastError text, and nothing launched, for n <= 0, k < 1, m < 0, n_seg
+ * outside [1, counters[8]], an odd or negative log_cap, log_cap below k, a kind this build does not have, or
+ * missing arrays.  Needs no scene; runs on the interface's device and stream with buffers of its own. */
+YAFARAY_C_API_EXPORT yafaray_bool_t yafaray_amd_queryPhotons(yafaray_Interface_t *interface, const float *pos, const float *dir, int n,
+                                                             const float *queries, const float *normals, int m, int k, float radius2, int n_seg,
+                                                             int log_cap, int kind, int *found, float *radius2_out, unsigned int *heap_idx,
+                                                             float *heap_dist, int *nearest, int *grid_raw, unsigned int *log_n,
+                                                             unsigned int *log_e, unsigned long long *counters);
 /* Test infrastructure (LIBYAFARAY_AMD_1.10): adaptive anti-aliasing's nextPass on a caller-supplied accumulated film.
  * accum: width x height x 4 floats (unnormalised), weights: width x height; tile: the tile size of the visiting
  * order; detect_color_noise ... variance_pixels: the AA noise parameters (dark_type 0 none, 1 linear, 2 curve);

@@ -145,6 +145,10 @@ def lib():
             "yafaray_amd_aaNextPass": (b, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i, i, i, i, i, f, i, i, f, i, i,
                                            C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                            C.POINTER(C.c_uint32)]),
+            "yafaray_amd_queryPhotons": (b, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                             i, i, f, i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                             C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32),
+                                             C.POINTER(C.c_uint32), C.POINTER(C.c_ulonglong)]),
             "yafaray_amd_getFilm": (b, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
             "yafaray_amd_getFilmDevice": (b, [vp, vp, i, i]),
             "yafaray_amd_getLayerCount": (i, [vp]),
@@ -507,6 +511,48 @@ class Interface:
                                              C.byref(count), C.byref(local)):
             raise RuntimeError("aaNextPass failed: " + self.last_error())
         return flags, plist[:local.value].copy(), count.value, local.value
+
+    QUERY_COUNTERS = ("visits", "accepts", "overflows", "depth", "pm_stack", "lds_levels", "spill", "path", "max_seg", "log_cap", "grid",
+                      "grid_ties", "photons", "kd_order")
+
+    def query_photons(self, pos, queries, kind, k=1, radius2=1e30, dirs=None, normals=None, n_seg=1, log_cap=0, want_log=False):
+        """Test infrastructure (yafaray_amd_queryPhotons): the photon-map queries of a render on the map of (n, 3)
+        positions (and directions, nearest kinds) for (m, 3) query points (and normals).  kind 0 - 5 (k-NN gathers)
+        return a dict with found (m,) int32, radius2 (m,) float32, idx (m, k) uint32 and dist (m, k) float32 in
+        heap-array order, counters (name -> int) and, with want_log, log_n (m,) and log_e (m, cap, 2) uint32;
+        kind 6 - 8 (nearest searches) return nearest (m,) int32, grid_raw (kind 7) and counters."""
+        fp, ip, up = C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_uint32)
+        arr = lambda a: None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+        pos, dirs, qs, ns = arr(pos), arr(dirs), arr(queries), arr(normals)
+        ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        n, m, k = len(pos), len(qs), int(k)
+        near = kind in (6, 7, 8)
+        counters = np.zeros(16, np.uint64)
+        out = {}
+        if near:
+            out["nearest"] = np.full(max(m, 1), -3, np.int32)
+            out["grid_raw"] = np.full(max(m, 1), -3, np.int32) if kind == 7 else None
+        else:
+            out["found"] = np.zeros(max(m, 1), np.int32)
+            out["radius2"] = np.zeros(max(m, 1), np.float32)
+            out["idx"] = np.zeros((max(m, 1), max(k, 1)), np.uint32)
+            out["dist"] = np.zeros((max(m, 1), max(k, 1)), np.float32)
+        cap = 0
+        if want_log and not near:
+            cap = int(log_cap) if log_cap else (max(k, int(os.environ.get("YAFARAY_AMD_GATHER_LOG", "512"))) + 1) & ~1
+            out["log_n"] = np.zeros(max(m, 1), np.uint32)
+            out["log_e"] = np.zeros((max(m, 1), max(cap, 1), 2), np.uint32)
+        if not self.L.yafaray_amd_queryPhotons(self.h, ptr(pos, fp), ptr(dirs, fp), n, ptr(qs, fp), ptr(ns, fp), m, k, float(np.float32(radius2)),
+                                               int(n_seg), int(log_cap), int(kind), ptr(out.get("found"), ip), ptr(out.get("radius2"), fp),
+                                               ptr(out.get("idx"), up), ptr(out.get("dist"), fp), ptr(out.get("nearest"), ip),
+                                               ptr(out.get("grid_raw"), ip), ptr(out.get("log_n"), up), ptr(out.get("log_e"), up),
+                                               counters.ctypes.data_as(C.POINTER(C.c_ulonglong))):
+            raise RuntimeError("queryPhotons failed: " + self.last_error())
+        res = {key: (v[:m] if v is not None else None) for key, v in out.items()}
+        res["counters"] = {name: int(counters[j]) for j, name in enumerate(self.QUERY_COUNTERS)}
+        if want_log and not near:
+            assert res["counters"]["log_cap"] in (0, cap), "the log cap the wrapper sized for differs from the library's"
+        return res
 
 
 

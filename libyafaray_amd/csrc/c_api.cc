@@ -535,6 +535,35 @@ yafaray_bool_t yafaray_amd_thinRadPoints(yafaray_Interface_t *interface, const f
 	return rendererOf(interface)->thinRadPointsHost(pos, nrm, n, maxrad, mode, kept, n_kept, rounds) ? YAFARAY_BOOL_TRUE : YAFARAY_BOOL_FALSE;
 }
 
+yafaray_bool_t yafaray_amd_queryPhotons(yafaray_Interface_t *interface, const float *pos, const float *dir, int n, const float *queries,
+                                        const float *normals, int m, int k, float radius2, int n_seg, int log_cap, int kind, int *found,
+                                        float *radius2_out, unsigned int *heap_idx, float *heap_dist, int *nearest, int *grid_raw,
+                                        unsigned int *log_n, unsigned int *log_e, unsigned long long *counters)
+{
+	GpuRenderer::PhotonQuery q;
+	q.pos3 = pos;
+	q.dir3 = dir;
+	q.n = n;
+	q.query3 = queries;
+	q.normal3 = normals;
+	q.m = m;
+	q.k = k;
+	q.radius2 = radius2;
+	q.n_seg = n_seg;
+	q.log_cap = log_cap;
+	q.kind = kind;
+	q.found = found;
+	q.radius2_out = radius2_out;
+	q.heap_idx = heap_idx;
+	q.heap_dist = heap_dist;
+	q.nearest = nearest;
+	q.grid_raw = grid_raw;
+	q.log_n = log_n;
+	q.log_e = log_e;
+	q.counters = counters;
+	return rendererOf(interface)->queryPhotonsHost(q) ? YAFARAY_BOOL_TRUE : YAFARAY_BOOL_FALSE;
+}
+
 yafaray_bool_t yafaray_amd_aaNextPass(yafaray_Interface_t *interface, const float *accum, const float *weights, int width, int height, int tile,
                                       int detect_color_noise, int dark_type, float dark_factor, int variance_edge, int variance_pixels,
                                       float threshold, int ry0, int ry1, unsigned char *flags, unsigned int *plist, unsigned int *count,

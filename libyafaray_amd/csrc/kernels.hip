@@ -4612,7 +4612,11 @@ __device__ __forceinline__ void replayLog(const H &heap, const uint2 *lg, uint32
 
 // HS (REPLAY without a caustic map): the split 6-byte heap (HeapRefSplit) — 1.5 -> 2 waves / SIMD at
 // k = 50; a request whose log overflowed walks again with the heap in its own log (8 B slots in HBM).
-template<bool SMALL, bool EXT, bool REPLAY = false, bool HS = false>
+// PROBE (test infrastructure, yafaray_amd_queryPhotons; false in every launch of a render): the lookup or replay
+// of a diffuse request as above, then the request's heap is written out instead of the estimate: A.samples is a
+// word array with 2 + 2 k words per query (k = S.pm_search), query = the request's sample id: photons found, the
+// final squared radius, k heap indices and k heap distances in heap-array order (the first `found` of each set).
+template<bool SMALL, bool EXT, bool REPLAY = false, bool HS = false, bool PROBE = false>
 __global__ void __launch_bounds__(kGatherBlock) k_gather(GatherArgs A)
 {
 	extern __shared__ uint4 gather_smem[];
@@ -4696,6 +4700,21 @@ __global__ void __launch_bounds__(kGatherBlock) k_gather(GatherArgs A)
 		}
 		photons += (uint32_t)found;
 		const float4 wk = A.G.wo_k[j];
+		if(PROBE)
+		{
+			const uint32_t k = (uint32_t)S.pm_search;
+			uint32_t *o = reinterpret_cast<uint32_t *>(A.samples) + (size_t)__float_as_uint(wk.w) * (2u + 2u * k);
+			o[0] = (uint32_t)found;
+			o[1] = __float_as_uint(max_d2);
+			for(int i = 0; i < found; ++i)
+			{
+				// (the split heap's slots hold log positions; after an overflow the heap is the log's first slots)
+				const uint32_t at = HS ? (from_log ? (uint32_t)hsplit.i(i) : (uint32_t)i) : 0u;
+				o[2 + i] = HS ? lg[at].x : heap.i(i);
+				o[2 + k + i] = HS ? (from_log ? __float_as_uint(hsplit.d(i)) : lg[at].y) : __float_as_uint(heap.d(i));
+			}
+			continue;
+		}
 		const uint4 cb = A.G.pix_mode[j];
 		Surf sp = surfFromPrim(S, p, __float_as_int(pp.w));
 		if(ATTR) applyAttr(sp, A.G.attr[2 * (size_t)j], A.G.attr[2 * (size_t)j + 1]);
@@ -4839,6 +4858,9 @@ struct PreGatherArgs
 	DevStats *stats;   // [0]: pre_visits / pre_photons of the launch (bench.py's byte model), or null
 };
 
+// PROBE (test infrastructure, yafaray_amd_queryPhotons; false in a render): S.pm_radius2 is the squared radius itself
+// and the heap is written out instead of the radiance estimate (A.out_pos as k_gather's probe words, query = j)
+template<bool PROBE = false>
 __global__ void __launch_bounds__(kGatherBlock) k_pregather(PreGatherArgs A)
 {
 	extern __shared__ uint4 gather_smem[];
@@ -4849,7 +4871,7 @@ __global__ void __launch_bounds__(kGatherBlock) k_pregather(PreGatherArgs A)
 	heap.stride = kGatherBlock;
 	const uint32_t gstride = gridDim.x * kGatherBlock;
 	uint2 *stk = S.pk_stack + blockIdx.x * kGatherBlock + threadIdx.x;
-	const float ds_radius_2 = S.pm_radius2 * S.pm_radius2;   // :42 ds_rad * ds_rad (pm_radius2 holds ds_rad)
+	const float ds_radius_2 = PROBE ? S.pm_radius2 : S.pm_radius2 * S.pm_radius2;   // :42 ds_rad * ds_rad (pm_radius2 holds ds_rad)
 	uint32_t visits = 0, found_sum = 0;
 	for(uint32_t j = blockIdx.x * kGatherBlock + threadIdx.x; j < A.n; j += gstride)
 	{
@@ -4859,6 +4881,20 @@ __global__ void __launch_bounds__(kGatherBlock) k_pregather(PreGatherArgs A)
 		const C3 refl = C3{a.w, b.w, c.x}, transm = C3{c.y, c.z, c.w};
 		float radius = ds_radius_2;
 		const int found = pkLookup(S.pk_nodes, pos, S.pm_search, radius, heap, stk, gstride, visits);
+		if(PROBE)
+		{
+			const uint32_t k = (uint32_t)S.pm_search;
+			uint32_t *o = reinterpret_cast<uint32_t *>(A.out_pos) + (size_t)j * (2u + 2u * k);
+			o[0] = (uint32_t)found;
+			o[1] = __float_as_uint(radius);
+			for(int i = 0; i < found; ++i)
+			{
+				o[2 + i] = heap.i(i);
+				o[2 + k + i] = __float_as_uint(heap.d(i));
+			}
+			found_sum += (uint32_t)found;
+			continue;
+		}
 		C3 sum = c3(0.f);
 		if(found > 0)
 		{
@@ -5080,6 +5116,45 @@ __device__ __forceinline__ int pkNearestLds(const uint4 *nodes, const float4 *di
 		if(!more) break;
 	}
 	return nearest;
+}
+
+// Test infrastructure (yafaray_amd_queryPhotons): the nearest searches themselves on caller-supplied points, at
+// kTraceBlock with the LDS column k_fg gives pkNearestLds (one word per level and lane, stride kTraceBlock).
+// mode 0: pkNearest; 1: pkNearestLds with `cap` levels; 2: gridNearest, then on -2 the kd search as k_fg_first
+// asks it (the private-array pkNearest; without a grid every query takes it) — out_grid keeps gridNearest's answer.
+struct NearestProbeArgs
+{
+	const uint4 *nodes;
+	const float4 *dirs;
+	RadGrid grid;
+	const float4 *qp, *qn;
+	uint32_t m;
+	float max_d2;
+	int mode, cap;
+	int *out, *out_grid;
+	unsigned long long *visits;
+};
+
+__global__ void __launch_bounds__(kTraceBlock) k_nearest_probe(NearestProbeArgs A)
+{
+	extern __shared__ uint32_t nearest_smem[];
+	uint32_t *nstk = nearest_smem + threadIdx.x;
+	uint32_t visits = 0;
+	for(uint32_t q = blockIdx.x * kTraceBlock + threadIdx.x; q < A.m; q += gridDim.x * kTraceBlock)
+	{
+		const V3 p = xyz(A.qp[q]), n = xyz(A.qn[q]);
+		int res;
+		if(A.mode == 1) res = pkNearestLds<kTraceBlock>(A.nodes, A.dirs, p, n, A.max_d2, nstk, A.cap, visits);
+		else if(A.mode == 2)
+		{
+			const int g = A.grid.start ? gridNearest(A.grid, p, n, A.max_d2, visits) : -2;
+			A.out_grid[q] = g;
+			res = g == -2 ? pkNearest(A.nodes, A.dirs, p, n, A.max_d2, &visits) : g;
+		}
+		else res = pkNearest(A.nodes, A.dirs, p, n, A.max_d2, &visits);
+		A.out[q] = res;
+	}
+	if(visits) atomicAdd(A.visits, (unsigned long long)visits);
 }
 
 // MonteCarloIntegrator::doLightEstimation for one light (integrator_montecarlo.cc:80-408) with the
@@ -6478,7 +6553,7 @@ hipError_t yafamd_photon_compact(const PhotonState *P, uint32_t *scratch_counts,
 }
 
 hipError_t yafamd_launch_gather(const DevScene *S, const DevNeeQueue *G, const DevCounters *cnt_next, float4 *samples,
-                                const DevJob *jobs, int n_jobs, uint64_t chunk_base, const GatherLogDesc *log, hipStream_t st)
+                                const DevJob *jobs, int n_jobs, uint64_t chunk_base, const GatherLogDesc *log, hipStream_t st, uint32_t *probe_out)
 {
 	GatherArgs A;
 	A.S = *S;
@@ -6501,6 +6576,16 @@ hipError_t yafamd_launch_gather(const DevScene *S, const DevNeeQueue *G, const D
 	const bool split = replay && log->split && !S->caus_map && log->cap <= 65536u && !YAF_GATHER_STACK_LDS;
 	const size_t lds = gatherTableBytes(*S, small) +
 	                   (split ? (size_t)kGatherBlock * 6u * (size_t)gatherHeapSlots(*S) : gatherLdsBytes(*S));
+	// the probe form (yafaray_amd_queryPhotons): the same grid, LDS layout and heap choice; the heaps go to probe_out
+	if(probe_out)
+	{
+		if(small || S->ext || S->caus_map) return hipErrorInvalidValue;
+		A.samples = reinterpret_cast<float4 *>(probe_out);
+		if(split) hipLaunchKernelGGL((k_gather<false, false, true, true, true>), grid, dim3(kGatherBlock), lds, st, A);
+		else if(replay) hipLaunchKernelGGL((k_gather<false, false, true, false, true>), grid, dim3(kGatherBlock), lds, st, A);
+		else hipLaunchKernelGGL((k_gather<false, false, false, false, true>), grid, dim3(kGatherBlock), lds, st, A);
+		return hipGetLastError();
+	}
 #define YAF_GATHER_LAUNCH(SM, E) \
 	do { if(split) hipLaunchKernelGGL((k_gather<SM, E, true, true>), grid, dim3(kGatherBlock), lds, st, A); \
 	     else if(replay) hipLaunchKernelGGL((k_gather<SM, E, true>), grid, dim3(kGatherBlock), lds, st, A); \
@@ -6550,6 +6635,8 @@ int yafamd_walk_threads(const DevScene *S) { return (int)(S->n_seg * kWalkPerSeg
 // the largest k the two-pass gather serves: the register walk's k; experiments builds also the bounded
 // walk (the split replay heap's 16-bit log positions bound it)
 int yafamd_gather_walk_k() { return kExperiments ? 65535 : kWalkK; }
+// the largest k of the register walk (k_gather_walk<false>)
+int yafamd_walk_exact_k() { return kWalkK; }
 
 // Final gathering: compaction of the radiance points (reuses the photon count / scan kernels on
 // rad_flag); *total_dev receives the count
@@ -6574,7 +6661,7 @@ hipError_t yafamd_rad_refl(const DevScene *S, float4 *a, float4 *b, float4 *c, c
 // preGatherWorker over the kept radiance points (n of them, indices `kept` into the compacted
 // arrays); the grid is the gather grid, whose lanes the HBM lookup stack (S->pk_stack) is sized for
 hipError_t yafamd_pregather(const DevScene *S, const float4 *a, const float4 *b, const float4 *c, const uint32_t *kept, uint32_t n,
-                            float4 *out_pos, float4 *out_dir, float *out_colb, DevStats *stats, hipStream_t st)
+                            float4 *out_pos, float4 *out_dir, float *out_colb, DevStats *stats, hipStream_t st, uint32_t *probe_out)
 {
 	if(n == 0) return hipSuccess;
 	PreGatherArgs A;
@@ -6589,7 +6676,13 @@ hipError_t yafamd_pregather(const DevScene *S, const float4 *a, const float4 *b,
 	A.out_colb = out_colb;
 	A.stats = stats;
 	const size_t lds = (size_t)kGatherBlock * 8u * (size_t)max(1, S->pm_search);
-	hipLaunchKernelGGL(k_pregather, dim3(S->n_seg * kGatherPerSeg), dim3(kGatherBlock), lds, st, A);
+	if(probe_out)
+	{
+		// (yafaray_amd_queryPhotons: the heaps instead of the estimates)
+		A.out_pos = reinterpret_cast<float4 *>(probe_out);
+		hipLaunchKernelGGL(k_pregather<true>, dim3(S->n_seg * kGatherPerSeg), dim3(kGatherBlock), lds, st, A);
+	}
+	else hipLaunchKernelGGL(k_pregather<false>, dim3(S->n_seg * kGatherPerSeg), dim3(kGatherBlock), lds, st, A);
 	return hipGetLastError();
 }
 
@@ -6723,6 +6816,20 @@ hipError_t yafamd_launch_fg_paths(const DevScene *S, const DevNeeQueue *G, const
 size_t yafamd_gather_lanes(const DevScene *S) { return (size_t)S->n_seg * (kWalkPerSeg > kGatherPerSeg ? kWalkPerSeg : kGatherPerSeg) * kGatherBlock; }
 
 size_t yafamd_gather_lds_bytes(const DevScene *S) { return gatherTableBytes(*S, S->small_tables != 0) + gatherLdsBytes(*S); }
+
+// k_nearest_probe (yafaray_amd_queryPhotons) over m points: mode 0 pkNearest, 1 pkNearestLds with `cap` LDS levels,
+// 2 the grid with the kd search on ties; at most two workgroups, so a lane serves several points
+hipError_t yafamd_nearest_probe(const uint4 *nodes, const float4 *dirs, const RadGrid *grid, const float4 *qp, const float4 *qn, uint32_t m,
+                                float max_d2, int mode, int cap, int *out, int *out_grid, unsigned long long *visits, hipStream_t st)
+{
+	if(m == 0) return hipSuccess;
+	if(mode < 0 || mode > 2 || (mode == 1 && (cap < 1 || cap > 32)) || (mode == 2 && !out_grid)) return hipErrorInvalidValue;
+	NearestProbeArgs A{nodes, dirs, grid ? *grid : RadGrid{}, qp, qn, m, max_d2, mode, cap, out, out_grid, visits};
+	const uint32_t blocks = min((m + kTraceBlock - 1u) / kTraceBlock, 2u);
+	const size_t lds = (size_t)(mode == 1 ? cap : 1) * kTraceBlock * sizeof(uint32_t);
+	hipLaunchKernelGGL(k_nearest_probe, dim3(blocks), dim3(kTraceBlock), lds, st, A);
+	return hipGetLastError();
+}
 
 hipError_t yafamd_launch_trace_rays(const DevScene *S, int any, const float4 *ro, const float4 *rd, int n, float *t_out,
                                     int *prim_out, int stack_depth, hipStream_t st)

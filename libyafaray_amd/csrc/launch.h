@@ -54,15 +54,20 @@ hipError_t yafamd_photon_bounce(const yafamd::DevScene *S, const yafamd::PhotonS
 hipError_t yafamd_photon_compact(const yafamd::PhotonState *P, uint32_t *scratch_counts, uint32_t *total_dev, float4 *pos, float4 *dir, float *colb,
                                  hipStream_t st);
 hipError_t yafamd_launch_gather(const yafamd::DevScene *S, const yafamd::DevNeeQueue *G, const yafamd::DevCounters *cnt_next, float4 *samples,
-                                const yafamd::DevJob *jobs, int n_jobs, uint64_t chunk_base, const yafamd::GatherLogDesc *log, hipStream_t st);
+                                const yafamd::DevJob *jobs, int n_jobs, uint64_t chunk_base, const yafamd::GatherLogDesc *log, hipStream_t st,
+                                uint32_t *probe_out = nullptr);
 hipError_t yafamd_launch_gather_walk(const yafamd::DevScene *S, const yafamd::DevNeeQueue *G, const yafamd::DevCounters *cnt_next, const yafamd::GatherLogDesc *log,
                                      hipStream_t st);
 int yafamd_gather_walk_k();
+int yafamd_walk_exact_k();
 size_t yafamd_gather_lds_bytes(const yafamd::DevScene *S);
 hipError_t yafamd_rad_compact(const yafamd::PhotonState *P, uint32_t *scratch_counts, uint32_t *total_dev, float4 *a, float4 *b, float4 *c, hipStream_t st);
 hipError_t yafamd_rad_refl(const yafamd::DevScene *S, float4 *a, float4 *b, float4 *c, const uint32_t *kept, uint32_t n, hipStream_t st);
 hipError_t yafamd_pregather(const yafamd::DevScene *S, const float4 *a, const float4 *b, const float4 *c, const uint32_t *kept, uint32_t n,
-                            float4 *out_pos, float4 *out_dir, float *out_colb, yafamd::DevStats *stats, hipStream_t st);
+                            float4 *out_pos, float4 *out_dir, float *out_colb, yafamd::DevStats *stats, hipStream_t st, uint32_t *probe_out = nullptr);
+// (test infrastructure, yafaray_amd_queryPhotons) the nearest searches on caller-supplied points
+hipError_t yafamd_nearest_probe(const uint4 *nodes, const float4 *dirs, const yafamd::RadGrid *grid, const float4 *qp, const float4 *qn, uint32_t m,
+                                float max_d2, int mode, int cap, int *out, int *out_grid, unsigned long long *visits, hipStream_t st);
 int yafamd_fg_paths_eligible(const yafamd::DevScene *S);
 hipError_t yafamd_launch_fg_paths(const yafamd::DevScene *S, const yafamd::DevNeeQueue *G, const yafamd::DevCounters *cnt_next, int stack_depth, int *spill, int grid,
                                   const yafamd::FgBatch *B, hipStream_t st);

@@ -2408,29 +2408,44 @@ bool GpuRenderer::Run::allocChunk()
 	return true;
 }
 
+// which gather serves a diffuse map searched with k photons per request, and the walk's log and heap settings
+// (setupGather, and yafaray_amd_queryPhotons kind 0)
+struct GatherChoice
+{
+	bool walk;        // k_gather_walk + k_gather<REPLAY>, else the one-pass k_gather
+	uint32_t cap;     // log entries per request (even: pairs)
+	uint32_t split, exact;   // GatherLogDesc
+};
+static GatherChoice gatherChoice(int k)
+{
+	const char *ge = std::getenv("YAFARAY_AMD_GATHER");
+	const bool single = ge && std::string(ge) == "single";
+	const char *ce = std::getenv("YAFARAY_AMD_GATHER_LOG");
+	const uint32_t cap = ((uint32_t)std::max(k, ce ? atoi(ce) : 512) + 1u) & ~1u;   // even: pairs
+	const char *he = std::getenv("YAFARAY_AMD_GATHER_HEAP");
+	const uint32_t split = (he && std::string(he) == "packed") ? 0u : 1u;
+	const char *we = std::getenv("YAFARAY_AMD_GATHER_WALK");
+	// the walk with the k smallest distances in registers (k <= 64): the bounded walk
+	// (YAFARAY_AMD_GATHER_WALK=bound, experiments builds; there also any k > 64) measured slower on C5
+	// (walk 13.9 -> 16.3 ms, replay 7.4 -> 12.1 ms per frame: its superset log); without it a larger
+	// k takes the one-pass gather (yafamd_gather_walk_k)
+	const uint32_t exact = (yafamd_experiments() && we && std::string(we) == "bound") ? 0u : 1u;
+	return GatherChoice{k <= yafamd_gather_walk_k() && !single, cap, split, exact};
+}
+
 // The two-pass diffuse gather (k_gather_walk + k_gather<REPLAY>, kernels.hip): its log holds `cap`
 // logged photons per request for a batch of
 // seg_cap queue positions per segment (within 16 GB); YAFARAY_AMD_GATHER=single keeps one pass.
 bool GpuRenderer::Run::setupGather()
 {
-	const char *ge = std::getenv("YAFARAY_AMD_GATHER");
-	const bool single = ge && std::string(ge) == "single";
-	if(S.gather_on && S.n_photons > 0 && S.pm_search <= yafamd_gather_walk_k() && !single)
+	const GatherChoice gc = gatherChoice(S.pm_search);
+	if(S.gather_on && S.n_photons > 0 && gc.walk)
 	{
-		const char *ce = std::getenv("YAFARAY_AMD_GATHER_LOG");
-		const uint32_t cap = ((uint32_t)std::max(S.pm_search, ce ? atoi(ce) : 512) + 1u) & ~1u;   // even: pairs
+		const uint32_t cap = gc.cap;
 		size_t seg_cap = S.cap_a;
 		while((size_t)R * seg_cap * cap * 8 > (16ull << 30) && seg_cap > 64) seg_cap = ((seg_cap / 2 + 63) / 64) * 64;
 		if(!ensure(log_, d.g_log, (size_t)R * seg_cap * cap * 8) || !ensure(log_, d.g_log_n, (size_t)R * seg_cap * 4)) return false;
-		const char *he = std::getenv("YAFARAY_AMD_GATHER_HEAP");
-		const uint32_t split = (he && std::string(he) == "packed") ? 0u : 1u;
-		const char *we = std::getenv("YAFARAY_AMD_GATHER_WALK");
-		// the walk with the k smallest distances in registers (k <= 64): the bounded walk
-		// (YAFARAY_AMD_GATHER_WALK=bound, experiments builds; there also any k > 64) measured slower on C5
-		// (walk 13.9 -> 16.3 ms, replay 7.4 -> 12.1 ms per frame: its superset log); without it a larger
-		// k takes the one-pass gather (yafamd_gather_walk_k)
-		const uint32_t exact = (yafamd_experiments() && we && std::string(we) == "bound") ? 0u : 1u;
-		glog = GatherLogDesc{d.g_log.p, (uint32_t *)d.g_log_n.p, cap, (uint32_t)seg_cap, 0u, split, exact, nullptr};
+		glog = GatherLogDesc{d.g_log.p, (uint32_t *)d.g_log_n.p, cap, (uint32_t)seg_cap, 0u, gc.split, gc.exact, nullptr};
 		// the walk's far-child stack levels beyond the LDS ones (tuning builds: -DYAF_WALK_LDS_LEVELS)
 		const int lv = yafamd_walk_lds_levels(d.pm_stack), deep = std::max(1, d.pm_stack) - lv;
 		if(deep > 0)
@@ -3749,6 +3764,299 @@ bool GpuRenderer::aaNextPassHost(const float *accum, const float *weights, int W
 	*count = c;
 	*local_count = lc;
 	return true;
+}
+
+// Test infrastructure (yafaray_amd_queryPhotons): the photon-map queries of a render on a caller-supplied map.
+// The tree is built by the production builder with buildMapTree's leaf-order rule (YAFARAY_AMD_PKD_ORDER; the
+// kd-order copies carry each photon's own index in the colour column, so every answer names the caller's photon),
+// the m query points become diffuse gather requests dealt over n_seg queue segments (dealRagged: segment 0 is
+// empty when n_seg > 1) and go through the launches a render makes — yafamd_launch_gather_walk unchanged, and
+// yafamd_launch_gather / yafamd_pregather in their probe form, which writes each request's heap out in heap-array
+// order instead of evaluating the material.  Nothing of the renderer's own maps or scratch is touched.
+// kind: 0 the render's choice (gatherChoice), 1 one-pass k_gather, 2 k_pregather, 3 / 4 the register walk with the
+// packed / split replay heap, 5 the bounded walk (experiments builds), 6 pkNearest, 7 the radiance grid with the kd
+// search on ties, 8 pkNearestLds (log_cap > 0: that many LDS levels instead of depth + 1).
+bool GpuRenderer::queryPhotonsHost(const PhotonQuery &Q)
+{
+	const bool near_kind = Q.kind >= 6 && Q.kind <= 8;
+	if(Q.kind < 0 || Q.kind > 8) { log_.error("GPU: queryPhotons: kind must lie in [0, 8]"); return false; }
+	if(Q.n <= 0 || !Q.pos3) { log_.error("GPU: queryPhotons: the map needs at least one photon"); return false; }
+	if(Q.m < 0 || (Q.m && !Q.query3) || !Q.counters || (Q.log_e && !Q.log_n)) { log_.error("GPU: queryPhotons: bad query arrays"); return false; }
+	if(!near_kind && Q.k < 1) { log_.error("GPU: queryPhotons: k must be at least 1"); return false; }
+	if(!near_kind && Q.k > 65535) { log_.error("GPU: queryPhotons: k above 65535"); return false; }
+	if(Q.log_cap < 0 || ((Q.log_cap & 1) && Q.kind != 8)) { log_.error("GPU: queryPhotons: log_cap must be even (pairs) and not negative"); return false; }
+	if(near_kind ? (!Q.dir3 || (Q.m && (!Q.normal3 || !Q.nearest || (Q.kind == 7 && !Q.grid_raw))))
+	             : (Q.m && (!Q.found || !Q.radius2_out || !Q.heap_idx || !Q.heap_dist)))
+	{
+		log_.error("GPU: queryPhotons: bad arrays for this kind");
+		return false;
+	}
+	if(Q.kind == 5 && !yafamd_experiments()) { log_.error("GPU: queryPhotons: the bounded walk (kind 5) exists in experiments builds only"); return false; }
+	if((Q.kind == 3 || Q.kind == 4) && Q.k > yafamd_walk_exact_k())
+	{
+		log_.error("GPU: queryPhotons: the register walk (kinds 3 and 4) serves k <= " + std::to_string(yafamd_walk_exact_k()));
+		return false;
+	}
+	if(!ready()) return false;
+	DeviceGuard guard(device_);
+	Impl &d = *d_;
+	if(Q.n_seg < 1 || Q.n_seg > d.shade_grid)
+	{
+		log_.error("GPU: queryPhotons: n_seg must lie in [1, " + std::to_string(d.shade_grid) + "]");
+		return false;
+	}
+	// the path: kind 0 takes the render's
+	const GatherChoice gc = gatherChoice(Q.k);
+	int path = Q.kind;
+	if(Q.kind == 0) path = !gc.walk ? 1 : (!gc.exact || Q.k > yafamd_walk_exact_k()) ? 5 : (gc.split && gc.cap <= 65536u) ? 4 : 3;
+	const bool walk = path >= 3 && path <= 5;
+	const uint32_t cap = Q.log_cap > 0 ? (uint32_t)Q.log_cap : gc.cap;
+	if(walk && cap < (uint32_t)Q.k) { log_.error("GPU: queryPhotons: log_cap below k (a render's log holds at least k entries)"); return false; }
+	if(path == 4 && cap > 65536u) { log_.error("GPU: queryPhotons: the split heap's 16-bit log positions need log_cap <= 65536"); return false; }
+
+	const size_t n = (size_t)Q.n, m = (size_t)Q.m, k = near_kind ? 1 : (size_t)Q.k;
+	// what depends on the tree's depth only (the builder halves every node: level d holds ceil(n / 2^d) photons at
+	// most) and on the requests' layout is refused here, before anything is launched
+	int want_depth = 0;
+	for(size_t c = n; c > 1; c = (c + 1) / 2) ++want_depth;
+	const int lds_cap = Q.kind == 8 ? (Q.log_cap > 0 ? Q.log_cap : want_depth + 1) : 0;
+	if(lds_cap > 32) { log_.error("GPU: queryPhotons: pkNearestLds keeps at most 32 levels (a render takes pkNearest then)"); return false; }
+	const std::vector<uint32_t> cnt = near_kind ? std::vector<uint32_t>() : dealRagged((uint32_t)m, (uint32_t)Q.n_seg, 0u);
+	const uint32_t cap_a = near_kind ? 1u : std::max(1u, *std::max_element(cnt.begin(), cnt.end()));
+	const uint32_t seg_cap = ((cap_a + 63u) / 64u) * 64u;
+	if(walk && (size_t)Q.n_seg * seg_cap * cap * 8 > (8ull << 30)) { log_.error("GPU: queryPhotons: the log of this n_seg, m and log_cap exceeds 8 GB"); return false; }
+	if(!near_kind)
+	{
+		DevScene probe{};
+		probe.n_photons = Q.n;
+		probe.pm_search = Q.k;
+		if(yafamd_gather_lds_bytes(&probe) > (size_t)64 * 1024) { log_.error("GPU: queryPhotons: k needs more than 64 KB of heap per workgroup"); return false; }
+	}
+	// kind 0 replays with the heap a render would; the kinds that name a walk name their heap too (5: packed)
+	const bool split_heap = path == 4 || (Q.kind == 0 && path == 5 && gc.split && cap <= 65536u);
+	struct Bufs
+	{
+		Buf pos, dir, colb, nodes, kpos, kdir, kcolb, qp, qn, wo, extra, cnt, stats, stack, out, log, log_n, spill, ident, near, near_grid, visits;
+		void *pkd_scratch = nullptr, *grid_scratch = nullptr;
+		~Bufs()
+		{
+			for(Buf *b : {&pos, &dir, &colb, &nodes, &kpos, &kdir, &kcolb, &qp, &qn, &wo, &extra, &cnt, &stats, &stack, &out, &log, &log_n, &spill,
+			              &ident, &near, &near_grid, &visits})
+				b->release();
+			if(pkd_scratch) yafamd_pkd_scratch_free(pkd_scratch);
+			if(grid_scratch) yafamd_rad_grid_free(grid_scratch);
+		}
+	} B;
+	for(int i = 0; i < QC_COUNT; ++i) Q.counters[i] = 0;
+	Q.counters[QC_MAX_SEG] = (unsigned long long)d.shade_grid;
+	Q.counters[QC_PATH] = (unsigned long long)path;
+
+	// ---- the map and its tree ----
+	std::vector<float4> pos(n), dir(n);
+	std::vector<uint32_t> own(n);
+	for(size_t i = 0; i < n; ++i)
+	{
+		pos[i] = make_float4(Q.pos3[3 * i], Q.pos3[3 * i + 1], Q.pos3[3 * i + 2], 0.f);
+		dir[i] = Q.dir3 ? make_float4(Q.dir3[3 * i], Q.dir3[3 * i + 1], Q.dir3[3 * i + 2], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+		own[i] = (uint32_t)i;
+	}
+	const char *oe = std::getenv("YAFARAY_AMD_PKD_ORDER");
+	const bool kd = !(oe && std::string(oe) == "photon");
+	int depth = 0;
+	if(!allocCopy(log_, B.pos, pos.data(), n) || !allocCopy(log_, B.dir, dir.data(), n) || !allocCopy(log_, B.colb, own.data(), n) ||
+	   !ensure(log_, B.nodes, (2 * n - 1) * 16))
+		return false;
+	if(kd)
+	{
+		if(!ensure(log_, B.kpos, n * 16) || !ensure(log_, B.kdir, n * 16) || !ensure(log_, B.kcolb, n * 4)) return false;
+		HIPCHECK(yafamd_build_pkd_kd((const float4 *)B.pos.p, (const float4 *)B.dir.p, (const float *)B.colb.p, (uint32_t)n, (uint4 *)B.nodes.p,
+		                             (float4 *)B.kpos.p, (float4 *)B.kdir.p, (float *)B.kcolb.p, &depth, d.stream, &B.pkd_scratch));
+		HIPCHECK(hipStreamSynchronize(d.stream));
+		HIPCHECK(hipMemcpy(own.data(), B.kcolb.p, n * 4, hipMemcpyDeviceToHost));
+		for(size_t i = 0; i < n; ++i)
+			if(own[i] >= n) { log_.error("GPU: queryPhotons: the kd-order copies lost a photon's index"); return false; }
+	}
+	else
+	{
+		HIPCHECK(yafamd_build_pkd((const float4 *)B.pos.p, (uint32_t)n, (uint4 *)B.nodes.p, &depth, d.stream, &B.pkd_scratch));
+		HIPCHECK(hipStreamSynchronize(d.stream));
+	}
+	const float4 *map_pos = (const float4 *)(kd ? B.kpos.p : B.pos.p), *map_dir = (const float4 *)(kd ? B.kdir.p : B.dir.p);
+	if(depth != want_depth) { log_.error("GPU: queryPhotons: the built tree's depth is not a balanced tree's"); return false; }
+	const int pm_stack = depth + 1;
+	Q.counters[QC_DEPTH] = (unsigned long long)depth;
+	Q.counters[QC_PM_STACK] = (unsigned long long)pm_stack;
+	Q.counters[QC_KD_ORDER] = kd ? 1u : 0u;
+	auto ownerOf = [&](uint32_t leaf, bool &ok) -> uint32_t {
+		if(leaf >= n) { ok = false; return 0xffffffffu; }
+		return own[leaf];
+	};
+	std::vector<float4> qp(std::max<size_t>(m, 1), make_float4(0.f, 0.f, 0.f, 0.f));
+	for(size_t i = 0; i < m; ++i) qp[i] = make_float4(Q.query3[3 * i], Q.query3[3 * i + 1], Q.query3[3 * i + 2], 0.f);
+
+	// ---- nearest kinds ----
+	if(near_kind)
+	{
+		if(Q.kind == 8) Q.counters[QC_LDS_LEVELS] = (unsigned long long)lds_cap;
+		if(m == 0) return true;
+		std::vector<float4> qn(m);
+		for(size_t i = 0; i < m; ++i) qn[i] = make_float4(Q.normal3[3 * i], Q.normal3[3 * i + 1], Q.normal3[3 * i + 2], 0.f);
+		RadGrid grid{};
+		if(Q.kind == 7)
+		{
+			const hipError_t e = yafamd_rad_grid(map_pos, map_dir, (uint32_t)n, Q.radius2, &grid, d.stream, &B.grid_scratch);
+			if(e != hipSuccess)
+			{
+				// (as publishRadianceMap: a grid too large or a radius of no extent leaves the kd search)
+				if(e != hipErrorNotSupported) { log_.error(std::string("GPU: queryPhotons: radiance grid: ") + hipGetErrorString(e)); return false; }
+				(void)hipGetLastError();
+				grid = RadGrid{};
+			}
+			Q.counters[QC_GRID] = grid.start ? 1u : 0u;
+		}
+		if(!allocCopy(log_, B.qp, qp.data(), m) || !allocCopy(log_, B.qn, qn.data(), m) || !ensure(log_, B.near, m * 4) ||
+		   !ensure(log_, B.near_grid, m * 4) || !ensure(log_, B.visits, 8))
+			return false;
+		HIPCHECK(hipMemsetAsync(B.visits.p, 0, 8, d.stream));
+		HIPCHECK(yafamd_nearest_probe((const uint4 *)B.nodes.p, map_dir, &grid, (const float4 *)B.qp.p, (const float4 *)B.qn.p, (uint32_t)m, Q.radius2,
+		                              Q.kind == 6 ? 0 : Q.kind == 8 ? 1 : 2, lds_cap, (int *)B.near.p, (int *)B.near_grid.p,
+		                              (unsigned long long *)B.visits.p, d.stream));
+		HIPCHECK(hipStreamSynchronize(d.stream));
+		HIPCHECK(hipMemcpy(Q.nearest, B.near.p, m * 4, hipMemcpyDeviceToHost));
+		HIPCHECK(hipMemcpy(&Q.counters[QC_VISITS], B.visits.p, 8, hipMemcpyDeviceToHost));
+		if(Q.kind == 7) HIPCHECK(hipMemcpy(Q.grid_raw, B.near_grid.p, m * 4, hipMemcpyDeviceToHost));
+		bool ok = true;
+		for(size_t i = 0; i < m; ++i)
+		{
+			if(Q.nearest[i] >= 0) Q.nearest[i] = (int)ownerOf((uint32_t)Q.nearest[i], ok);
+			if(Q.kind == 7 && Q.grid_raw[i] >= 0) Q.grid_raw[i] = (int)ownerOf((uint32_t)Q.grid_raw[i], ok);
+			if(Q.kind == 7 && Q.grid_raw[i] == -2) ++Q.counters[QC_GRID_TIES];
+		}
+		if(!ok) log_.error("GPU: queryPhotons: a search returned a photon outside the map");
+		return ok;
+	}
+
+	// ---- gather kinds: the requests, dealt over the segments ----
+	const size_t NA = (size_t)cap_a * Q.n_seg, words = 2 + 2 * k;
+	std::vector<float4> p_prim(NA, make_float4(0.f, 0.f, 0.f, 0.f)), wo(NA, make_float4(0.f, 0.f, 1.f, 0.f)), extra(NA, make_float4(0.f, 0.f, 0.f, 0.f));
+	{
+		uint32_t i = 0;
+		const uint32_t mode = G_DIFFUSE;
+		for(int s = 0; s < Q.n_seg; ++s)
+			for(uint32_t j = 0; j < cnt[s]; ++j, ++i)
+			{
+				const size_t at = (size_t)s * cap_a + j;
+				p_prim[at] = qp[i];
+				std::memcpy(&wo[at].w, &i, 4);
+				std::memcpy(&extra[at].w, &mode, 4);
+			}
+	}
+	DevScene S{};
+	S.pk_nodes = (const uint4 *)B.nodes.p;
+	S.ph_pos = map_pos;
+	S.ph_dir = map_dir;
+	S.n_photons = (int)n;
+	S.pm_paths = 1;
+	S.pm_search = Q.k;
+	S.pm_radius2 = Q.radius2;
+	S.pm_stack = pm_stack;
+	S.gather_on = 1;
+	S.n_seg = (uint32_t)Q.n_seg;
+	S.cap_a = cap_a;
+	if(!allocCopy(log_, B.qp, p_prim.data(), NA) || !allocCopy(log_, B.wo, wo.data(), NA) || !allocCopy(log_, B.extra, extra.data(), NA) ||
+	   !allocCopy(log_, B.cnt, cnt.data(), cnt.size()) || !ensure(log_, B.stats, sizeof(DevStats) * (size_t)Q.n_seg) ||
+	   !ensure(log_, B.stack, (size_t)pm_stack * yafamd_gather_lanes(&S) * sizeof(uint2)) || !ensure(log_, B.out, std::max<size_t>(m, 1) * words * 4))
+		return false;
+	HIPCHECK(hipMemsetAsync(B.stats.p, 0, sizeof(DevStats) * (size_t)Q.n_seg, d.stream));
+	HIPCHECK(hipMemsetAsync(B.out.p, 0, std::max<size_t>(m, 1) * words * 4, d.stream));
+	S.pk_stack = (uint2 *)B.stack.p;
+	S.stats = (DevStats *)B.stats.p;
+	DevNeeQueue G{};
+	G.p_prim = (float4 *)B.qp.p;
+	G.wo_k = (float4 *)B.wo.p;
+	G.extra = (float4 *)B.extra.p;
+	DevCounters C{};
+	C.n_gather = (uint32_t *)B.cnt.p;
+	Q.counters[QC_LDS_LEVELS] = (unsigned long long)(walk ? yafamd_walk_lds_levels(pm_stack) : 0);
+	if(path == 2)
+	{
+		// k_pregather: the points are its radiance points (kept = every one), the stack its pk_stack column
+		std::vector<uint32_t> ident(std::max<size_t>(m, 1));
+		for(size_t i = 0; i < ident.size(); ++i) ident[i] = (uint32_t)i;
+		if(!allocCopy(log_, B.ident, ident.data(), ident.size()) || !allocCopy(log_, B.qn, qp.data(), qp.size())) return false;
+		HIPCHECK(yafamd_pregather(&S, (const float4 *)B.qn.p, (const float4 *)B.qn.p, (const float4 *)B.qn.p, (const uint32_t *)B.ident.p, (uint32_t)m,
+		                          nullptr, nullptr, nullptr, (DevStats *)B.stats.p, d.stream, (uint32_t *)B.out.p));
+	}
+	else if(walk)
+	{
+		if(!ensure(log_, B.log, (size_t)Q.n_seg * seg_cap * cap * 8) || !ensure(log_, B.log_n, (size_t)Q.n_seg * seg_cap * 4)) return false;
+		GatherLogDesc L{B.log.p, (uint32_t *)B.log_n.p, cap, seg_cap, 0u, split_heap ? 1u : 0u, path == 5 ? 0u : 1u, nullptr};
+		const int deep = std::max(1, pm_stack) - yafamd_walk_lds_levels(pm_stack);
+		if(deep > 0 && path != 5)
+		{
+			if(!ensure(log_, B.spill, (size_t)deep * yafamd_walk_threads(&S) * 4)) return false;
+			L.spill = (uint32_t *)B.spill.p;
+			Q.counters[QC_SPILL] = 1;
+		}
+		Q.counters[QC_LOG_CAP] = cap;
+		HIPCHECK(hipMemsetAsync(B.log_n.p, 0, (size_t)Q.n_seg * seg_cap * 4, d.stream));
+		HIPCHECK(yafamd_launch_gather_walk(&S, &G, &C, &L, d.stream));
+		if(Q.log_n || Q.log_e)
+		{
+			// the raw log, before the replay (an overflowed request's heap takes its place in the log)
+			HIPCHECK(hipStreamSynchronize(d.stream));
+			size_t i0 = 0;
+			for(int s = 0; s < Q.n_seg; ++s)
+			{
+				if(!cnt[s]) continue;
+				if(Q.log_n) HIPCHECK(hipMemcpy(Q.log_n + i0, (const uint32_t *)B.log_n.p + (size_t)s * seg_cap, (size_t)cnt[s] * 4, hipMemcpyDeviceToHost));
+				if(Q.log_e)
+					HIPCHECK(hipMemcpy(Q.log_e + i0 * cap * 2, (const uint2 *)B.log.p + (size_t)s * seg_cap * cap, (size_t)cnt[s] * cap * 8, hipMemcpyDeviceToHost));
+				i0 += cnt[s];
+			}
+		}
+		HIPCHECK(yafamd_launch_gather(&S, &G, &C, nullptr, nullptr, 0, 0, &L, d.stream, (uint32_t *)B.out.p));
+	}
+	else HIPCHECK(yafamd_launch_gather(&S, &G, &C, nullptr, nullptr, 0, 0, nullptr, d.stream, (uint32_t *)B.out.p));
+	HIPCHECK(hipStreamSynchronize(d.stream));
+	std::vector<uint32_t> out(std::max<size_t>(m, 1) * words);
+	std::vector<DevStats> st((size_t)Q.n_seg);
+	HIPCHECK(hipMemcpy(out.data(), B.out.p, out.size() * 4, hipMemcpyDeviceToHost));
+	HIPCHECK(hipMemcpy(st.data(), B.stats.p, sizeof(DevStats) * st.size(), hipMemcpyDeviceToHost));
+	for(const DevStats &b : st)
+	{
+		Q.counters[QC_VISITS] += b.gather_visits + b.pre_visits;
+		Q.counters[QC_ACCEPTS] += b.gather_accepts;
+		Q.counters[QC_OVERFLOWS] += b.gather_overflows;
+		Q.counters[QC_PHOTONS] += b.gather_photons + b.pre_photons;
+	}
+	bool ok = true;
+	for(size_t i = 0; i < m; ++i)
+	{
+		const uint32_t *o = out.data() + i * words;
+		const uint32_t f = o[0];
+		if(f > k) { ok = false; break; }
+		Q.found[i] = (int)f;
+		std::memcpy(&Q.radius2_out[i], &o[1], 4);
+		for(size_t j = 0; j < k; ++j)
+		{
+			Q.heap_idx[i * k + j] = j < f ? ownerOf(o[2 + j], ok) : 0xffffffffu;
+			if(j < f) std::memcpy(&Q.heap_dist[i * k + j], &o[2 + k + j], 4);
+			else Q.heap_dist[i * k + j] = 0.f;
+		}
+	}
+	if(Q.log_e && walk && kd)
+	{
+		// the log names leaves too: the caller's photon for every entry a request logged
+		for(size_t i = 0; i < m; ++i)
+			for(uint32_t a = 0, na = std::min(Q.log_n[i], cap); a < na; ++a)
+			{
+				uint32_t &e = Q.log_e[(i * cap + a) * 2];
+				e = ownerOf(e, ok);
+			}
+	}
+	if(!ok) log_.error("GPU: queryPhotons: a lookup returned more than k photons or a photon outside the map");
+	return ok;
 }
 
 // ---------------------------------------------------------------------------------------------

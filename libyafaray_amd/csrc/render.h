@@ -252,6 +252,27 @@ class GpuRenderer
 		bool thinRadPointsHost(const float *pos3, const float *nrm3, int n, float maxrad, int mode, uint32_t *kept, int *n_kept, int *rounds);
 		bool aaNextPassHost(const float *accum, const float *weights, int W, int H, int tile, const DevAaParams &prm, float threshold, int ry0,
 		                    int ry1, uint8_t *flags, uint32_t *plist, uint32_t *count, uint32_t *local_count);
+		// test infrastructure (yafaray_amd_queryPhotons): photon-map queries on a caller-supplied map (render.cc)
+		struct PhotonQuery
+		{
+			const float *pos3 = nullptr, *dir3 = nullptr;   // n photons
+			int n = 0;
+			const float *query3 = nullptr, *normal3 = nullptr;   // m query points
+			int m = 0, k = 0;
+			float radius2 = 0.f;
+			int n_seg = 1, log_cap = 0, kind = 0;
+			// gather kinds: per query, k heap slots each; nearest kinds: nearest (and the grid's own answer, kind 7)
+			int *found = nullptr;
+			float *radius2_out = nullptr;
+			uint32_t *heap_idx = nullptr;
+			float *heap_dist = nullptr;
+			int *nearest = nullptr, *grid_raw = nullptr;
+			uint32_t *log_n = nullptr, *log_e = nullptr;   // kinds 0, 3 - 5: the walk's raw log (m counts, m x cap x 2 words)
+			unsigned long long *counters = nullptr;        // QC_COUNT values
+		};
+		enum : int { QC_VISITS = 0, QC_ACCEPTS, QC_OVERFLOWS, QC_DEPTH, QC_PM_STACK, QC_LDS_LEVELS, QC_SPILL, QC_PATH, QC_MAX_SEG, QC_LOG_CAP,
+		             QC_GRID, QC_GRID_TIES, QC_PHOTONS, QC_KD_ORDER, QC_COUNT = 16 };
+		bool queryPhotonsHost(const PhotonQuery &q);
 		bool buildPhotonMap(RenderParams &rp);
 		bool buildRadianceMap(RenderParams &rp);
 		bool shootMap(RenderParams &rp, const PhotonSet &L, uint32_t N, int bounces, int which, uint32_t &n_out, int &depth_out);

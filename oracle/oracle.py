@@ -331,6 +331,57 @@ def thin_rad_points(pos, nrm, maxrad):
     return kept[:nk].copy()
 
 
+def photon_tree(pos):
+    """The reference's point kd-tree over (n, 3) positions (yc_photon_tree): (nodes, depth) with nodes a (2n - 1, 2)
+    uint32 array of (data, flags) words (PkNode: flags bits 0-1 axis, 3 = leaf, bits 2.. right child; data = split
+    bits or photon index) and depth the deepest level (root = 0)."""
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    n = len(pos)
+    nodes = np.empty((2 * n - 1, 2), np.uint32)
+    depth = C.c_int(0)
+    lib = oracle_lib()
+    lib.yc_photon_tree.restype = C.c_int
+    if lib.yc_photon_tree(_p(pos, C.c_float), C.c_int(n), _p(nodes, C.c_uint32), C.byref(depth)) != 2 * n - 1:
+        raise RuntimeError("yc_photon_tree failed")
+    return nodes, depth.value
+
+
+def photon_gather(pos, queries, k, radius2):
+    """PhotonMap::gather (yc_photon_gather, the lookup the oracle's render runs) of (m, 3) query points in the map of
+    (n, 3) positions: (found (m,) int32, final squared radius (m,) float32, heap indices (m, k) uint32, heap squared
+    distances (m, k) float32) in heap-array order; slots beyond found hold 0xffffffff / 0."""
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    qs = np.ascontiguousarray(queries, np.float32).reshape(-1, 3)
+    n, m, k = len(pos), len(qs), int(k)
+    found = np.zeros(max(m, 1), np.int32)
+    r2 = np.zeros(max(m, 1), np.float32)
+    idx = np.zeros((max(m, 1), max(k, 1)), np.uint32)
+    dist = np.zeros((max(m, 1), max(k, 1)), np.float32)
+    lib = oracle_lib()
+    lib.yc_photon_gather.restype = C.c_int
+    if not lib.yc_photon_gather(_p(pos, C.c_float), C.c_int(n), _p(qs, C.c_float), C.c_int(m), C.c_int(k), C.c_float(np.float32(radius2)),
+                                _p(found, C.c_int), _p(r2, C.c_float), _p(idx, C.c_uint32), _p(dist, C.c_float)):
+        raise RuntimeError("yc_photon_gather: bad arguments")
+    return found[:m], r2[:m], idx[:m], dist[:m]
+
+
+def photon_nearest(pos, dirs, queries, normals, radius2):
+    """PhotonMap::findNearest (yc_photon_nearest) of (m, 3) query points / normals in the map of (n, 3) positions /
+    directions: the (m,) int32 photon indices, -1 where none faces the normal within the radius."""
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    qs = np.ascontiguousarray(queries, np.float32).reshape(-1, 3)
+    ns = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    assert len(dirs) == len(pos) and len(ns) == len(qs)
+    out = np.zeros(max(len(qs), 1), np.int32)
+    lib = oracle_lib()
+    lib.yc_photon_nearest.restype = C.c_int
+    if not lib.yc_photon_nearest(_p(pos, C.c_float), _p(dirs, C.c_float), C.c_int(len(pos)), _p(qs, C.c_float), _p(ns, C.c_float),
+                                 C.c_int(len(qs)), C.c_float(np.float32(radius2)), _p(out, C.c_int)):
+        raise RuntimeError("yc_photon_nearest: bad arguments")
+    return out[:len(qs)]
+
+
 def aa_next_pass(accum, weights, threshold, detect_color_noise=False, dark_type=0, dark_factor=0.0, variance_edge=10,
                  variance_pixels=0):
     """ImageFilm::nextPass's resample flags ((H, W) uint8) of an accumulated film ((H, W, 4), (H, W)): the

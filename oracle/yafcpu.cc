@@ -3747,6 +3747,91 @@ int yc_thin_rad_points(const float *pos, const float *nrm, int n, float maxrad, 
 	return (int)k.size();
 }
 
+// ---- photon-map queries on caller-supplied maps (the lookups the oracle's render runs: Renderer::gather and
+// Renderer::findNearest over Renderer::buildPhotonTree's tree) ----
+static void photonQueryMap(Renderer::PhotonMapData &M, const float *pos, const float *dir, int n)
+{
+	M.photons.resize((size_t)std::max(0, n));
+	for(int i = 0; i < n; ++i)
+	{
+		M.photons[i].pos = V3(pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2]);
+		M.photons[i].dir = dir ? V3(dir[3 * (size_t)i], dir[3 * (size_t)i + 1], dir[3 * (size_t)i + 2]) : V3(0.f, 0.f, 0.f);
+		M.photons[i].col = C3(0.f);
+	}
+	Renderer::buildPhotonTree(M);
+}
+
+// deepest level of the tree (root = 0)
+static int photonTreeDepth(const Renderer::PhotonMapData &M)
+{
+	int depth = 0;
+	std::vector<std::pair<uint32_t, int>> todo;
+	if(M.ready()) todo.push_back({0u, 0});
+	while(!todo.empty())
+	{
+		const auto [node, level] = todo.back();
+		todo.pop_back();
+		depth = std::max(depth, level);
+		if(M.nodes[node].isLeaf()) continue;
+		todo.push_back({node + 1u, level + 1});
+		todo.push_back({M.nodes[node].right(), level + 1});
+	}
+	return depth;
+}
+
+// the point kd-tree over n positions: 2n - 1 nodes of (data, flags) words (PkNode) and the deepest level
+int yc_photon_tree(const float *pos, int n, uint32_t *nodes, int *depth)
+{
+	if(!pos || n < 1) return 0;
+	Renderer::PhotonMapData M;
+	photonQueryMap(M, pos, nullptr, n);
+	if(nodes)
+		for(size_t i = 0; i < M.nodes.size(); ++i) { nodes[2 * i] = M.nodes[i].data; nodes[2 * i + 1] = M.nodes[i].flags; }
+	if(depth) *depth = photonTreeDepth(M);
+	return (int)M.nodes.size();
+}
+
+// PhotonMap::gather for m query points: found[q] photons, final squared radius r2[q], and the heap as it stands
+// when the lookup returns, in array order: idx / dist hold k slots per query, the first found[q] of them set
+// (the others 0xffffffff / 0)
+int yc_photon_gather(const float *pos, int n, const float *queries, int m, int k, float radius2, int *found, float *r2, uint32_t *idx,
+                     float *dist)
+{
+	if(!pos || n < 1 || k < 1 || m < 0 || (m && (!queries || !found || !r2 || !idx || !dist))) return 0;
+	Renderer::PhotonMapData M;
+	photonQueryMap(M, pos, nullptr, n);
+	std::vector<Renderer::Found> heap((size_t)k);
+	for(int q = 0; q < m; ++q)
+	{
+		float r = radius2;
+		const V3 p(queries[3 * (size_t)q], queries[3 * (size_t)q + 1], queries[3 * (size_t)q + 2]);
+		const int f = Renderer::gather(M, p, heap.data(), (uint32_t)k, r);
+		found[q] = f;
+		r2[q] = r;
+		for(int i = 0; i < k; ++i)
+		{
+			idx[(size_t)q * k + i] = i < f ? heap[i].photon : 0xffffffffu;
+			dist[(size_t)q * k + i] = i < f ? heap[i].dist_square : 0.f;
+		}
+	}
+	return 1;
+}
+
+// PhotonMap::findNearest for m query points and normals: nearest[q] = the photon's index, -1: none
+int yc_photon_nearest(const float *pos, const float *dir, int n, const float *queries, const float *normals, int m, float radius2, int *nearest)
+{
+	if(!pos || !dir || n < 1 || m < 0 || (m && (!queries || !normals || !nearest))) return 0;
+	Renderer::PhotonMapData M;
+	photonQueryMap(M, pos, dir, n);
+	for(int q = 0; q < m; ++q)
+	{
+		const V3 p(queries[3 * (size_t)q], queries[3 * (size_t)q + 1], queries[3 * (size_t)q + 2]);
+		const V3 nn(normals[3 * (size_t)q], normals[3 * (size_t)q + 1], normals[3 * (size_t)q + 2]);
+		nearest[q] = Renderer::findNearest(M, p, nn, radius2);
+	}
+	return 1;
+}
+
 void yc_round_to_int(const double *v, int *out, int n) { for(int i = 0; i < n; ++i) out[i] = roundToInt(v[i]); }
 void yc_floor_to_int(const double *v, int *out, int n) { for(int i = 0; i < n; ++i) out[i] = floorToInt(v[i]); }
 void yc_clamp_proportional(const float *rgb, float max_value, float *out, int n)

@@ -276,5 +276,13 @@ int yc_aa_next_pass(const float *accum, const float *weights, int W, int H, int 
                     int variance_edge, int variance_pixels, float threshold, uint8_t *flags);
 // the radiance-point thinning (integrator_photon_mapping.cc:560-572): the kept indices, ascending; returns their count
 int yc_thin_rad_points(const float *pos, const float *nrm, int n, float maxrad, uint32_t *kept);
+// photon-map queries over caller-supplied maps (pkdtree.h:115-292, photon.cc:31-64, 136-142): the point kd-tree
+// (2n - 1 nodes of (data, flags) words; *depth: deepest level, root = 0; returns the node count), the k-NN gather
+// (per query: photons found, final squared radius, the heap in array order: k slots of index and squared
+// distance) and findNearest (-1: none); the last two return 0 on bad arguments
+int yc_photon_tree(const float *pos, int n, uint32_t *nodes, int *depth);
+int yc_photon_gather(const float *pos, int n, const float *queries, int m, int k, float radius2, int *found, float *r2, uint32_t *idx,
+                     float *dist);
+int yc_photon_nearest(const float *pos, const float *dir, int n, const float *queries, const float *normals, int m, float radius2, int *nearest);
 
 }
