@@ -11,8 +11,13 @@
 //  * FAST_TRIG parabolic sin/cos (math.h:218-250) and the Faure-scrambled Halton sequences
 //    (src/sampler/halton.cc:421-441) in double precision, which is IEEE on gfx950.
 //
-// The header is also compiled for the host (tests/test_devmath.py builds a tiny g++ harness
-// that checks x87mul*() against real long double on millions of inputs).
+// The header is checked on both compilers.  tests/test_devmath.py builds it with g++ for the host
+// (tests/devmath_host.cc, devmath_check.cc) and checks x87mul*() against real long double, the libm
+// restatements against the host's libm and the samplers against the reference's golden vectors, on
+// millions of inputs.  tests/test_devmath_gpu.py builds it, with texeval.h, for gfx950 with the
+// device units' own flags (tests/devmath_dev.hip, `make devcheck`) and compares what the device
+// computes with that g++ build and the same golden vectors bit for bit, on the same inputs and on
+// the near-midpoint inputs that take the exact paths.
 #pragma once
 
 #include <cstdint>

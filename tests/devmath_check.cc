@@ -37,7 +37,8 @@ int main(int argc, char **argv)
 	const long n = argc > 1 ? atol(argv[1]) : 2000000;
 	std::mt19937_64 rng(12345);
 	std::uniform_real_distribution<float> u(-30.f, 30.f), s(0.f, 1.f), pos(1e-4f, 50.f);
-	long bad_mul = 0, bad_mul2 = 0, bad_div = 0, bad_sin = 0, bad_cos = 0, bad_hemi = 0;
+	long bad_mul = 0, bad_mul2 = 0, bad_mul3 = 0, bad_div = 0, bad_sin = 0, bad_cos = 0, bad_hemi = 0;
+	std::uniform_real_distribution<float> rad(0.01f, 2.f);
 	// the constants themselves
 	const X87Const cs[] = {kPi, kDivPiBy2, kDiv1ByPi, kMultPiBy2, kDiv1By2Pi, kDiv4ByPi, kDiv4BySquaredPi};
 	const LD ls[] = {pi, div_pi_by_2, div_1_by_pi, mult_pi_by_2, div_1_by_2pi, div_4_by_pi, div_4_by_squared_pi};
@@ -64,11 +65,25 @@ int main(int argc, char **argv)
 			if(x != 0.f && !same(x87mulExact(kDiv4ByPi.hi, kDiv4ByPi.lo, x), (float)(div_4_by_pi * x))) ++bad_mul;
 			if(x != 0.f && !same(x87mul2Exact(kDiv4BySquaredPi.hi, kDiv4BySquaredPi.lo, x, std::abs(x)), (float)(div_4_by_squared_pi * x * std::abs(x)))) ++bad_mul2;
 		}
+		{
+			// sample.h:31-35 kernel(d^2, 1 / r^2) = 3 ir2 / pi (1 - d^2 ir2)^2 as the gather kernels draw it (a gather
+			// radius, a photon inside it), then uniform positives; dispatcher and exact path on every input
+			const float r = rad(rng), ir2 = 1.f / (r * r), d2 = s(rng) * (r * r);
+			float sk = 1.f - d2 * ir2;
+			if(sk < 0.f) sk = 0.f;
+			const float k3[2][3] = {{3.f * ir2, sk, sk}, {pos(rng), pos(rng), pos(rng)}};
+			for(const auto &k : k3)
+			{
+				const float want = (float)(div_1_by_pi * k[0] * k[1] * k[2]);
+				if(!same(x87mul3(kDiv1ByPi, k[0], k[1], k[2]), want)) ++bad_mul3;
+				if(k[0] != 0.f && k[1] != 0.f && k[2] != 0.f && !same(x87mul3Exact(kDiv1ByPi.hi, kDiv1ByPi.lo, k[0], k[1], k[2]), want)) ++bad_mul3;
+			}
+		}
 		if(!same(fsin(x), refSin(x))) ++bad_sin;
 		if(!same(fcos(x), refSin(x + static_cast<float>(div_pi_by_2)))) ++bad_cos;
 		const float s2 = s(rng);
 		if(!same(x87mul(kMultPiBy2, s2), (float)(s2 * mult_pi_by_2))) ++bad_hemi;
 	}
-	printf("n=%ld const=%d mul=%ld mul2=%ld div=%ld sin=%ld cos=%ld hemi=%ld\n", n, bad_const, bad_mul, bad_mul2, bad_div, bad_sin, bad_cos, bad_hemi);
-	return (bad_const + bad_mul + bad_mul2 + bad_div + bad_sin + bad_cos + bad_hemi) ? 1 : 0;
+	printf("n=%ld const=%d mul=%ld mul2=%ld mul3=%ld div=%ld sin=%ld cos=%ld hemi=%ld\n", n, bad_const, bad_mul, bad_mul2, bad_mul3, bad_div, bad_sin, bad_cos, bad_hemi);
+	return (bad_const + bad_mul + bad_mul2 + bad_mul3 + bad_div + bad_sin + bad_cos + bad_hemi) ? 1 : 0;
 }

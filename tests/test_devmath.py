@@ -8,6 +8,8 @@ import tempfile
 import numpy as np
 import pytest
 
+import devmathlib as L
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = np.load(os.path.join(HERE, "golden", "prims.npz"))
 
@@ -29,7 +31,9 @@ def test_x87_emulation_vs_long_double():
     subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe, os.path.join(HERE, "devmath_check.cc")],
                    check=True)
     r = subprocess.run([exe, "400000"], capture_output=True, text=True)
+    print(r.stdout)
     assert r.returncode == 0, r.stdout + r.stderr
+    assert " mul3=0 " in r.stdout, r.stdout
 
 
 @pytest.mark.parametrize("which,name", [(0, "riVdC"), (1, "riS"), (2, "riLp")])
@@ -166,3 +170,69 @@ def test_sphere_v_long_double(dm):
     dm.dm_sphere_v(P(a, C.c_float), len(a), P(dev, C.c_float), P(ref, C.c_float))
     bad = dev.view(np.uint32) != ref.view(np.uint32)
     assert not bad.any(), f"{bad.sum()} differ, e.g. {a[bad][:3]}"
+
+
+def test_libm_asin_atan_match_host_libm():
+    """libmAsinf, libmAtanf and math::asin (AngularCamera::shootRay, the tube / sphere projections) against the host's
+    asinf / atanf on the recipe of test_libm_restatements_match_host_libm plus the edge values by name; atan2f and
+    acosf again through the same entry point, which tests/test_devmath_gpu.py uses as the device's reference."""
+    y, x = L.libm_inputs()
+    for name, (dev, ref) in L.host_libm(L.host_lib()).items():
+        same = L.same_bits(dev, ref)
+        assert same.all(), L.describe(name, same, dev, ref, y, x)
+
+
+def test_halton_next_and_inc_match_sequence():
+    """haltonNext(base, start, k) and HaltonInc<base>: start() then 16 next() calls, against all 16 values of every
+    recorded sequence; the three formulations against each other on random 32-bit starts."""
+    lib = L.host_lib()
+    for base, start, seq in zip(GOLD["halton_bases"], GOLD["halton_starts"], GOLD["halton_seq"]):
+        _, first, nxt, inc = L.halton(lib.dm_halton, base, [start])
+        assert np.array_equal(nxt[0].view(np.uint32), seq.view(np.uint32)), (base, start, nxt[0], seq)
+        assert np.array_equal(inc[0].view(np.uint32), seq.view(np.uint32)), (base, start, inc[0], seq)
+        assert first[0].view(np.uint32) == seq[0].view(np.uint32)
+    starts = np.random.default_rng(5).integers(0, 2 ** 32, 100_000, dtype=np.uint64).astype(np.uint32)
+    for base in (2, 3, 5):
+        _, first, nxt, inc = L.halton(lib.dm_halton, base, starts)
+        assert np.array_equal(nxt.view(np.uint32), inc.view(np.uint32)), base
+        assert np.array_equal(first.view(np.uint32), nxt[:, 0].view(np.uint32)), base
+
+
+def test_round64_round24_vs_long_double():
+    """round64 and round24, the two roundings every exact path ends with, on double-doubles made to hit each of their
+    cases (ties of the first rounding, float midpoints reached exactly after it, a power of two approached from below)
+    against real x87 arithmetic: the products reach such ties for about one input in 2^40, so no product test does."""
+    hi, lo = L.round_inputs()
+    n = len(hi)
+    r_hi, r_lo = np.empty(n), np.empty(n)
+    r24, ref24 = np.empty(n, np.float32), np.empty(n, np.float32)
+    ok64 = np.empty(n, np.int32)
+    L.host_lib().dm_round(L.P(hi, C.c_double), L.P(lo, C.c_double), n, L.P(r_hi, C.c_double), L.P(r_lo, C.c_double),
+                          L.P(r24, C.c_float), L.P(ok64, C.c_int32), L.P(ref24, C.c_float))
+    assert np.array_equal(r_hi, hi)
+    assert ok64.all(), f"round64: {(ok64 == 0).sum()} of {n} differ from the long double sum, e.g. {hi[ok64 == 0][:3]} {lo[ok64 == 0][:3]}"
+    same = L.same_bits(r24, ref24)
+    assert same.all(), L.describe("round24", same, r24, ref24, hi, lo)
+    assert (r_lo != lo).sum() > n // 4   # the first rounding is no identity on these inputs
+
+
+X87_CALLS = {"x87mul": ("dm_x87mul", 1), "x87mul2": ("dm_x87mul2", 2), "x87mul3": ("dm_x87mul3", 3),
+             "x87mulDiv": ("dm_x87muldiv", 2), "x87recipMul": ("dm_x87recip", 1)}
+
+
+@pytest.mark.parametrize("dispatcher", list(L.SCANS))
+def test_near_midpoint_inputs_take_the_exact_path(dispatcher):
+    """The binade scan finds the inputs that fail safeToRound (about 2e-6 of all), so the dispatcher's slow branch
+    runs on each of them: there it equals the *Exact function and the reference expression in real long double."""
+    lib = L.host_lib()
+    cases, total = L.near_midpoint(dispatcher)
+    print(f"{dispatcher}: {total} near-midpoint inputs")
+    assert total >= L.NEAR_MIN, f"{dispatcher}: only {total} near-midpoint inputs found"
+    fn, nargs = X87_CALLS[dispatcher]
+    for c, x, y, z in cases:
+        ops = (x, y, z)[:nargs]
+        disp, exact, ld = (np.empty(len(x), np.float32) for _ in range(3))
+        getattr(lib, fn)(c, *[L.P(o, C.c_float) for o in ops], L.P(disp, C.c_float), L.P(exact, C.c_float), L.P(ld, C.c_float), len(x))
+        for name, got in (("dispatcher", disp), ("exact", exact)):
+            same = L.same_bits(got, ld) & ~np.isnan(ld)
+            assert same.all(), L.describe(f"{dispatcher} {name} (constant {c})", same, got, ld, *ops)
