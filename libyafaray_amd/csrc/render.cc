@@ -2535,11 +2535,19 @@ bool GpuRenderer::Run::decideSchedule()
 	sch.overlap = rp.device_sharers <= 1;
 	sch.ov_nee_grid = std::max(1, (int)S.n_seg / 2);
 	sch.ov_trace_grid = std::max((int)S.n_seg, std::min(2 * (int)S.n_seg, d.trace_grid));
+	bool ov_grids_set = false;   // a grid variable is set: the early shadow part below keeps what it asks for
 	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP"); e && *e) sch.overlap = *e != '0';
-	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_NEE_GRID"); e && atoi(e) > 0) sch.ov_nee_grid = atoi(e);
+	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_NEE_GRID"); e && atoi(e) > 0)
+	{
+		sch.ov_nee_grid = atoi(e);
+		ov_grids_set = true;
+	}
 	// (k_trace's grid is a multiple of n_seg: segLoop)
 	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_TRACE_GRID"); e && atoi(e) > 0)
+	{
 		sch.ov_trace_grid = (int)S.n_seg * std::max(1, std::min(atoi(e), d.trace_grid) / (int)S.n_seg);
+		ov_grids_set = true;
+	}
 	sch.overlap = sch.overlap && S.scene_in_lds && !S.ray_sort && !S.brute && !sch.ray_bin && !S.tree && !S.tr_shad && !S.has_attr &&
 	              sch.nee_trace_stack == 0;
 	// The shadow part beside the closest part (YAFARAY_AMD_OVERLAP_SHADOW): the shadow rays of iteration it + 1
@@ -2560,6 +2568,19 @@ bool GpuRenderer::Run::decideSchedule()
 	if(const char *e = std::getenv("YAFARAY_AMD_OVERLAP_SHADOW_GRID"); e && atoi(e) > 0)
 		sch.ov_shadow_grid = (int)S.n_seg * std::max(1, std::min(atoi(e), d.trace_grid) / (int)S.n_seg);
 	sch.ov_shadow = sch.ov_shadow && sch.overlap && d.spill.p == nullptr;
+	// With the early shadow part and the flat scan the closest part became the shorter of the two chains between
+	// k_shade(it) and k_shade(it + 1) (18.4 against 26.7 ms per C2 frame for k_nee -> shadow part), so k_nee takes
+	// three quarters of the segments' workgroups (3 per CU instead of 2) and the closest part the grid it was
+	// given before it had to leave half of the register file, 4 n_seg: C2 51.1-52.8 -> 50.3-50.9 ms per frame,
+	// worst run under the parent's best in both sweeps (by 0.6 and 0.2 ms; mean -1.4 and -0.8 ms).  Launching
+	// k_nee and the shadow part per group of queue segments instead gained nothing beyond the noise with two
+	// groups and lost 8-11 ms with three and four, and was taken out again (profiles/c2_nee_groups.md).
+	// Without the early shadow part the split above stays.
+	if(sch.ov_shadow && !ov_grids_set)
+	{
+		sch.ov_nee_grid = std::max(1, 3 * (int)S.n_seg / 4);
+		sch.ov_trace_grid = std::max((int)S.n_seg, (int)S.n_seg * (std::min(4 * (int)S.n_seg, d.trace_grid) / (int)S.n_seg));
+	}
 	// k_trace's deferred leaf tests (upload() decided the capacity): every launch of the render, full or part,
 	// timed or with statistics, runs the same traversal.  Iteration 0 keeps the interleaved loop under either
 	// schedule: the coherent camera rays of a wave hit the same leaves at the same visits, so the lists only add
